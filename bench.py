@@ -1,7 +1,13 @@
 """KDLAE-T forward throughput on MI355X (BASELINE.json configs[1] / configs[4]).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps, the output
+dump when `--dump-outputs DIR` is given, and the result line.  Everything else described below
+(roofline probe passes, the bs=1 latency line, cpu_baseline / parity, the nested S8 / A64 / training
+legs) runs only with `--full`; there the `--no-*` and `--probe*` options select among those legs.
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (see dump_outputs).
 
 `--gpus N` (N > 1) without a torchrun environment starts the N rank processes itself (one per GPU,
 torch.distributed.run on 127.0.0.1, the reference's own launcher: Train/train.sh:5) before anything
@@ -15,7 +21,7 @@ hash-uniform images with per-image constant denoise_rate.
 
 Printed JSON (rank 0): value = images/s over all ranks (max-over-ranks wall time of exactly K
 steps between barriers + device syncs) of the module's default, un-instrumented forward (HIP-graph
-replay); roofline of the dominant kernel class measured live with HIP events around each of its
+replay).  With `--full`: roofline of the dominant kernel class measured live with HIP events around each of its
 launches in a separate probe pass of the same workload after the timed steps; cpu_baseline = the CPU oracle
 (oracle/kdlae_oracle.py, test infrastructure) on one image of the same workload, 1 warm-up + the
 median of 3 timed runs, whose output also gives the PSNR / max-abs of the GPU result
@@ -175,6 +181,38 @@ def cpu_timed(fn, runs: int = 3):
     return out, ts[len(ts) // 2], ts
 
 
+DUMP_BUDGET_BYTES = 60 << 20  # everything one run dumps stays under 64 MB
+
+
+def named_outputs(out, name="out"):
+    """What a caller of the timed path receives, as {name: tensor}: the module's dict as it is, a
+    single tensor under `name`, a tuple as name0, name1, ..."""
+    if isinstance(out, dict):
+        return {k: v for k, v in out.items() if v is not None}
+    if isinstance(out, (tuple, list)):
+        return {f"{name}{i}": v for i, v in enumerate(out) if v is not None}
+    return {name: out}
+
+
+def dump_outputs(dirpath, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: write every tensor of `arrays` as dirpath/<name>.npy (float32; a float64 tensor
+    stays float64).  The arrays share `budget` bytes equally.  One that fits its share is written
+    whole, in its own shape; a larger one is written as a fixed sample: the 1-D array of its elements
+    at the sorted flat indices np.random.default_rng(0).integers(0, numel, share // itemsize), so two
+    builds run with the same arguments dump the same elements."""
+    os.makedirs(dirpath, exist_ok=True)
+    share = budget // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach()
+        if t.dtype != torch.float64:
+            t = t.float()
+        keep = share // t.element_size()
+        if t.numel() > keep:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), keep))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirpath, f"{name}.npy"), t.cpu().numpy())
+
+
 def bench_standin(args, world, rank):
     """CPU rehearsal of the N-rank path (gloo, no GPU): the T16 sharding, timing and gather with a
     per-image stand-in for the forward.  Each rank sleeps rank-dependent time per step so the
@@ -199,6 +237,8 @@ def bench_standin(args, world, rank):
     if world > 1:
         info = [None] * world
         dist.all_gather_object(info, {"rank": rank, "first": rank * B, "last": rank * B + B - 1, "local_s": local})
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"hq": full})
     if rank == 0:
         gimg, grate = make_inputs(0, world * B, H, H)
         res = {"metric": METRIC + " [CPU stand-in rehearsal]", "value": round(world * B * args.steps / elapsed, 3),
@@ -241,9 +281,10 @@ def asdqe_flops(ci, d, B, H, W):
     return f
 
 
-def bench_secondary(args, world, rank, dev, distributed, workload, batch=0, size=0, cpu=True):
+def bench_secondary(args, world, rank, dev, distributed, workload, batch=0, size=0, cpu=True, dump=None):
     """S8 (KDLAE-S bs=8 4x512x512) and A64 (ASDQE bs=64 256x256): BASELINE.json configs[2], [3].
-    Returns the result dict (rank 0 prints it, or nests it in the T16 line)."""
+    Returns the result dict (rank 0 prints it, or nests it in the T16 line).  dump: --dump-outputs
+    directory when this workload is the run's own (not when nested in the T16 line)."""
     if workload == "s8":
         B = batch or 8
         Fr, H, W = 4, size or 512, size or 512
@@ -289,6 +330,8 @@ def bench_secondary(args, world, rank, dev, distributed, workload, batch=0, size
 
     elapsed, _, out = timed_steps(timed, 1, distributed, dev)
     dev_ms = ev0.elapsed_time(ev1)
+    if dump and rank == 0:
+        dump_outputs(dump, named_outputs(out))
     if distributed:  # the gathered outputs: this rank's shard is rows [rank*B, rank*B + B)
         out = out[rank * B:(rank + 1) * B]
     ach = flops * args.steps / (dev_ms / 1e3) / 1e12
@@ -412,7 +455,9 @@ def bench_train(args, world, rank, dev, distributed, nested=False):
            "final_loss": float(loss)}
     if nested:
         return res
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss})
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle.kdlae_oracle import TeacherCfg
         from oracle.train_oracle import TrainStep
         threads, tdesc = host_cores() if not args.cpu_threads else (args.cpu_threads, "--cpu-threads")
@@ -501,7 +546,9 @@ def bench_train_s(args, world, rank, dev, distributed):
                         "kernel": "whole training step (all launches, algorithmic 3x forward FLOPs)",
                         "algorithmic_flops_per_step": flops},
            "final_loss": float(loss)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss})
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle.kdlae_oracle import StudentCfg
         from oracle.train_oracle import YML_S_LOSS, student_loss_and_grads
         threads, tdesc = host_cores() if not args.cpu_threads else (args.cpu_threads, "--cpu-threads")
@@ -536,6 +583,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=0, help="images per GPU (0 = workload default)")
     ap.add_argument("--size", type=int, default=0, help="frame size (0 = workload default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         "(float32, at most 64 MB in all: a fixed seeded sample of a larger output)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: roofline probe passes, the bs=1 "
+                         "latency line, cpu_baseline / parity and (t16) the nested S8 / A64 / training legs; "
+                         "the --probe* and --no-* options below select among these and need --full")
     ap.add_argument("--probe", default="3,1",
                     help="kernel classes to probe, comma-separated; the first is the line's roofline (0 = off): "
                          "1 conv_gemm, 2 dwconv_gram, 3 feed-forward half")
@@ -585,7 +639,7 @@ def main():
         return bench_train_s(args, world, rank, dev, distributed)
     if args.workload != "t16":
         res = bench_secondary(args, world, rank, dev, distributed, args.workload, args.batch, args.size,
-                              cpu=not args.no_cpu_baseline)
+                              cpu=args.full and not args.no_cpu_baseline, dump=args.dump_outputs)
         if rank == 0:
             print(json.dumps(res), flush=True)
         if distributed:
@@ -625,6 +679,8 @@ def main():
     torch.cuda.synchronize(dev)
 
     elapsed, _, out = timed_steps(step, args.steps, distributed, dev, drain=drain)
+    if args.dump_outputs and rank == 0:  # the last timed step's hq / sr as the caller received them
+        dump_outputs(args.dump_outputs, named_outputs(out))
     if gather:  # this rank's own images of the gathered batch (for the parity leg)
         out = {k: (v[rank * B:(rank + 1) * B] if v is not None else None) for k, v in out.items()}
 
@@ -694,7 +750,7 @@ def main():
 
     # the first listed class is the line's `roofline` (the dominant class, by its share of the step);
     # the others are reported under `roofline_classes`
-    classes = [int(c) for c in str(args.probe).split(",") if c.strip() and int(c) != 0]
+    classes = [int(c) for c in str(args.probe).split(",") if c.strip() and int(c) != 0] if args.full else []
     roof, other = None, {}
     for i, cls in enumerate(classes):
         r = probe(cls)
@@ -704,7 +760,7 @@ def main():
             other[PROBE_CLASSES[cls]] = r
 
     bs1 = None
-    if not args.no_bs1 and B > 1 and world == 1:
+    if args.full and not args.no_bs1 and B > 1 and world == 1:
         # the metric names 1x512x512: single-image latency of the drop-in module's forward on the same
         # GPU, each call synchronised (HIP events on the forward's stream), after the throughput run.
         # The module's default forward replays a HIP graph for a repeated shape (KDLAE_teacher.hip_graphs);
@@ -770,9 +826,9 @@ def main():
                           # traffic; the fused kernels move less than that model, so >1 is possible
                           "vs_survey_unfused_sigma_max_roof": round(ips / 41.8, 4)}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"], res["parity"] = cpu_baseline(model, batch, out, args.cpu_threads)
-    if not args.no_secondary and not args.batch and not args.size:
+    if args.full and not args.no_secondary and not args.batch and not args.size:
         # BASELINE configs[2] / [3] timed in the same run (their own weights, inputs and buffers)
         del model, batch, out, eng
         torch.cuda.empty_cache()
@@ -781,7 +837,7 @@ def main():
             keep = ("metric", "value", "unit", "ms_per_step", "config", "roofline", "cpu_baseline", "parity")
             res[wl] = {k: sec[k] for k in keep if k in sec}
             torch.cuda.empty_cache()
-    if not args.no_train and not args.batch and not args.size:
+    if args.full and not args.no_train and not args.batch and not args.size:
         # SURVEY §8f rank 1, KDLAET.yml's 6 x 128^2 step, timed in the same run
         if "model" in locals():
             del model, batch, out, eng

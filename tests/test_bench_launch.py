@@ -74,8 +74,46 @@ def test_gpus_n_fails_without_enough_devices():
     assert not [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
 
 
-def test_standin_single_rank_matches_contract():
-    p = _bench("--cpu-standin", "--steps", "2", "--warmup", "0", "--batch", "3", "--size", "8")
+def test_standin_single_rank_matches_contract(tmp_path):
+    """The single-rank line, and --dump-outputs: the last timed step's output as DIR/<name>.npy, float32."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    d = str(tmp_path / "dump")
+    p = _bench("--cpu-standin", "--steps", "2", "--warmup", "0", "--batch", "3", "--size", "8", "--dump-outputs", d)
     assert p.returncode == 0, p.stderr[-3000:]
     res = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
     assert res["n_gpus"] == 1 and res["config"]["global_batch"] == 3 and res["standin"]["gather_equal"]
+    assert res["steps"] == 2 and res["ms_per_step"] > 0
+    assert os.listdir(d) == ["hq.npy"]
+    hq = np.load(os.path.join(d, "hq.npy"))
+    img, rate = bench.make_inputs(0, 3, 8, 8)  # the stand-in forward is img * 2 + rate
+    assert hq.dtype == np.float32 and np.array_equal(hq, (img * 2 + rate).numpy())
+
+
+def test_dump_outputs_samples_a_large_output(tmp_path):
+    """An output over its share of the byte budget is written as the same seeded sample every time;
+    one that fits is written whole; float64 stays float64, everything else becomes float32."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    big = torch.arange(5000, dtype=torch.float32).reshape(2, 50, 50)
+    arrays = {"big": big, "small": torch.ones(3, 4, dtype=torch.float64), "half": torch.full((5,), 0.5).half()}
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    bench.dump_outputs(a, arrays, budget=3 * 4000)  # 4000 bytes each: 1000 of big's 5000 floats
+    bench.dump_outputs(b, {k: v.clone() for k, v in arrays.items()}, budget=3 * 4000)
+    got = {n: np.load(os.path.join(a, n + ".npy")) for n in arrays}
+    assert sorted(os.listdir(a)) == ["big.npy", "half.npy", "small.npy"]
+    assert got["big"].dtype == np.float32 and got["big"].shape == (1000,)
+    idx = got["big"].astype(np.int64)  # big holds its own flat index
+    assert np.all(np.diff(idx) >= 0) and idx.min() >= 0 and idx.max() < 5000 and len(set(idx.tolist())) > 800
+    assert got["small"].dtype == np.float64 and got["small"].shape == (3, 4)
+    assert got["half"].dtype == np.float32 and np.array_equal(got["half"], np.full(5, 0.5, np.float32))
+    for n in arrays:
+        assert np.array_equal(got[n], np.load(os.path.join(b, n + ".npy")))
+    assert sum(os.path.getsize(os.path.join(a, f)) for f in os.listdir(a)) <= 3 * 4000 + 3 * 128  # + .npy headers

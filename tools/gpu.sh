@@ -110,7 +110,7 @@ ab)
       echo "$n: $(tail -1 $O/gputest_$n.log)"
     fi
     for c in ${PROBE:-1}; do
-      KDLAE_PROBE_DUMP=$O/probe_c${c}_$n.csv timeout -k 10 300 python -u bench.py --steps 2 --warmup 1 --probe $c --probe-steps 2 --no-cpu-baseline --no-bs1 --no-secondary > $O/probe_c${c}_$n.json 2> $O/probe_c${c}_$n.err || exit $?
+      KDLAE_PROBE_DUMP=$O/probe_c${c}_$n.csv timeout -k 10 300 python -u bench.py --full --steps 2 --warmup 1 --probe $c --probe-steps 2 --no-cpu-baseline --no-bs1 --no-secondary > $O/probe_c${c}_$n.json 2> $O/probe_c${c}_$n.err || exit $?
     done
     timeout -k 10 300 python -u bench.py --steps ${STEPS:-5} --warmup 2 --probe 0 --no-cpu-baseline --no-bs1 --no-secondary > $O/bench_$n.json 2> $O/bench_$n.err || exit $?
     echo "$n: $(head -c 150 $O/bench_$n.json)"
