@@ -358,6 +358,44 @@ int kdlae_train_l1frames(const float* pred, const float* target, int N, int fram
                          float temporal_weight, float binary, int reduction, float* dpred, float* loss, float* scratch,
                          void* stream);
 
+/* ------------------------------------------------------------------ ASDQE training
+ * One micro-batch of Train/ASDQE.py:95-122 on DenoiseRatePredictor in train mode: BatchNorm2d uses
+ * batch statistics over all B x H' x W' pixels (the zero-padded ones of pad_to_multiple included) and
+ * updates its running statistics (momentum 0.1), Dropout multiplies by caller-supplied masks.
+ * fp32 throughout.  Parameters / gradients: flat caller-owned buffers of asdqe_train_num_floats floats in
+ * named_parameters() order, every key 16-byte aligned (pads zero), as for kdlae_tt_* / kdlae_st_*;
+ * kdlae_train_clip_adamw / _ema apply unchanged.  BatchNorm running statistics: a second flat buffer
+ * of asdqe_train_num_stat_floats floats, per BatchNorm [running_mean | running_var] in state_dict
+ * order. */
+typedef struct asdqe_train_handle asdqe_train_handle;
+/* replaces DenoiseRatePredictor.__init__ for training (ASDQE_model.py:127-156); same limits as asdqe_create */
+int asdqe_train_create(const asdqe_config* cfg, int device, asdqe_train_handle** out);
+int asdqe_train_destroy(asdqe_train_handle* h);
+int asdqe_train_num_params(const asdqe_train_handle* h);
+int asdqe_train_param_info(const asdqe_train_handle* h, int index, const char** name, int64_t* numel, int64_t* offset);
+int64_t asdqe_train_num_floats(const asdqe_train_handle* h);
+int64_t asdqe_train_num_stat_floats(const asdqe_train_handle* h);
+/* Device bytes of the caller-owned workspace (saved activations + backward scratch); -1 (and
+ * kdlae_last_error) for a batch whose buffers cannot be indexed: B * H' * W' * 128 must be < 2^31. */
+int64_t asdqe_train_workspace_bytes(const asdqe_train_handle* h, int B, int H, int W);
+/* replaces `pred = model(lq, gt)` under model.train() (Train/ASDQE.py:103): lq, gt [B, in_channels, H, W];
+ * score [B, 1]; stats: the running statistics, updated in place; mask1 [B, 256] / mask2 [B, 64]: the two
+ * Dropouts' masks, already scaled (0 or 1 / (1 - p)), NULL = identity.  Activations stay in `workspace`
+ * for asdqe_train_backward. */
+int asdqe_train_forward(asdqe_train_handle* h, const float* theta, float* stats, const float* lq, const float* gt,
+                        int B, int H, int W, const float* mask1, const float* mask2, float* score, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+/* replaces `loss.backward()` (:107): dscore [B, 1] -> grad (flat; accumulate != 0: grad += d loss / d theta,
+ * else grad = ...; the reference accumulates over 32 micro-batches, :101-112).  The conv biases that feed a
+ * BatchNorm get exact zeros (their gradient is mathematically zero).  The images get no gradient.  One
+ * backward per forward: KDLAE_ESTATE when no forward is live. */
+int asdqe_train_backward(asdqe_train_handle* h, const float* theta, const float* dscore, float* grad, int accumulate,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+/* replaces nn.MSELoss()(pred, score) / accumulation_steps (Train/ASDQE.py:88,104-105) over n scores:
+ * loss[0] = mean((s - t)^2) (unscaled), loss[1] = mean |s - t| (the loop's MAE); dscore = scale 2 (s - t) / n. */
+int kdlae_train_mse(const float* score, const float* target, int n, float scale, float* dscore, float* loss,
+                    void* stream);
+
 /* ---- Kernel self-test entry points (tests/test_kernel_variants_gpu.py; not part of the drop-in
  * boundary).  One launch of the training GEMM family on caller device buffers:
  *   C(m, n) = sum_k A(m, k) B(k, n) [+ bias[n]] [+ rs[n] R(m, n)], batch z = z1 * nz2 + z2, every
@@ -463,6 +501,29 @@ typedef struct kdlae_debug_small_in_desc {
   int Bn, H, W, vh, vw, relu;
 } kdlae_debug_small_in_desc;
 int kdlae_debug_small_in(const kdlae_debug_small_in_desc* d, void* stream);
+
+/* ASDQE training kernels (bn_train.hip) over NHWC views (C % 4 == 0, every ld % 4 == 0), one op per call:
+ *   0 bn_stats: x [P][ldx] -> mean, rstd [C] (+ the running update of running_mean / running_var when given)
+ *   1 bn_apply_relu: out = relu((x - mean) rstd gamma + beta)
+ *   2 bn_bwd_reduce: (dy, y, x) -> dgamma, dbeta [C]
+ *   3 bn_bwd_dx: out = gamma rstd (dy [y > 0] - dbeta / P - xhat dgamma / P)
+ *   4 upsample2x_bwd: x = the [N][2h][2w] gradient -> out [N][h][w]       5 upsample2x: x [N][h][w] -> out
+ * part: scratch of >= 2048 C floats (ops 0, 2). */
+typedef struct kdlae_debug_bn_desc {
+  int op;
+  const float* x; int ldx;
+  const float* y; int ldy;
+  const float* dy; int ldd;
+  float* out; int ldo;
+  float* mean; float* rstd;
+  float* running_mean; float* running_var; float momentum;
+  const float* gamma; const float* beta;
+  float* dgamma; float* dbeta;
+  int C; int64_t P;
+  int N, h, w;
+  float* part; int64_t part_floats;
+} kdlae_debug_bn_desc;
+int kdlae_debug_bn(const kdlae_debug_bn_desc* d, void* stream);
 
 #ifdef __cplusplus
 }

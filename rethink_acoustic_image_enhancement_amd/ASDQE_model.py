@@ -110,8 +110,9 @@ class DenoiseRatePredictor(nn.Module):
     def forward(self, lq: torch.Tensor, gt: torch.Tensor, return_features: bool = False):
         """score [B, 1]; with ``return_features=True`` also the UNet output map [B, 3*dim, H', W']."""
         if self.training:
-            raise RuntimeError("DenoiseRatePredictor (MI355X build) is inference-only: call .eval() first "
-                               "(BatchNorm running statistics, Dropout off)")
+            raise RuntimeError("DenoiseRatePredictor.forward (MI355X build) is inference-only: call .eval() first "
+                               "(BatchNorm running statistics, Dropout off); to train, use train.ASDQETrainer "
+                               "or train.asdqe_train_forward")
         if lq.device.type != "cuda" or gt.device != lq.device:
             raise RuntimeError("DenoiseRatePredictor (MI355X build) runs on ROCm devices only; there is no CPU "
                                "fallback")

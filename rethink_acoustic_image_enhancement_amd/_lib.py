@@ -47,6 +47,10 @@ EXPORTS = (
     "kdlae_debug_gram",
     "kdlae_debug_ln",
     "kdlae_debug_small_in",
+    "asdqe_train_create", "asdqe_train_destroy", "asdqe_train_num_params", "asdqe_train_param_info",
+    "asdqe_train_num_floats", "asdqe_train_num_stat_floats", "asdqe_train_workspace_bytes", "asdqe_train_forward",
+    "asdqe_train_backward", "kdlae_train_mse",
+    "kdlae_debug_bn",
 )
 
 
@@ -188,13 +192,29 @@ def lib() -> ctypes.CDLL:
     L.kdlae_train_l1frames_scratch_floats.restype = c_int64
     L.kdlae_train_l1frames.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int64, ctypes.c_float, ctypes.c_float,
                                        ctypes.c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.asdqe_train_create.argtypes = [ctypes.POINTER(AConfig), c_int, ctypes.POINTER(c_void_p)]
+    L.asdqe_train_destroy.argtypes = [c_void_p]
+    L.asdqe_train_num_params.argtypes = [c_void_p]
+    L.asdqe_train_param_info.argtypes = [c_void_p, c_int, ctypes.POINTER(c_char_p), ctypes.POINTER(c_int64),
+                                         ctypes.POINTER(c_int64)]
+    L.asdqe_train_num_floats.argtypes = [c_void_p]
+    L.asdqe_train_num_floats.restype = c_int64
+    L.asdqe_train_num_stat_floats.argtypes = [c_void_p]
+    L.asdqe_train_num_stat_floats.restype = c_int64
+    L.asdqe_train_workspace_bytes.argtypes = [c_void_p, c_int, c_int, c_int]
+    L.asdqe_train_workspace_bytes.restype = c_int64
+    L.asdqe_train_forward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
+    L.asdqe_train_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p]
+    L.kdlae_train_mse.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_float, c_void_p, c_void_p, c_void_p]
+    L.kdlae_debug_bn.argtypes = [c_void_p, c_void_p]
     L.kdlae_debug_tgemm.argtypes = [c_void_p, c_void_p]
     for f in ("kdlae_debug_gemm", "kdlae_debug_gram", "kdlae_debug_ln", "kdlae_debug_small_in"):
         getattr(L, f).argtypes = [c_void_p, c_void_p]
     L.kdlae_debug_gemm_variant.argtypes = [c_int, c_int, ctypes.POINTER(c_int)]
     for name in EXPORTS:
         if not name.endswith(("_last_error", "_abi_version", "_workspace_bytes", "_padded_size", "_num_floats",
-                              "_scratch_floats", "_params_numel", "_mark_lo")):
+                              "_scratch_floats", "_params_numel", "_mark_lo", "_num_stat_floats")):
             getattr(L, name).restype = c_int
     _lib = L
     return L

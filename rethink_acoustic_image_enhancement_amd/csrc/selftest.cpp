@@ -9,6 +9,7 @@
 
 #include "../../include/kdlae.h"
 #include "runtime.h"
+#include "train_a.h"
 #include "train_kernels.h"
 
 namespace tr = kdlae::train;
@@ -228,5 +229,40 @@ extern "C" int kdlae_debug_small_in(const kdlae_debug_small_in_desc* d, void* st
   p.relu = d->relu;
   const hipError_t e = kdlae::launch_conv_small_in(p, (hipStream_t)stream);
   if (e != hipSuccess) return fail(KDLAE_EHIP, std::string("kdlae_debug_small_in: ") + hipGetErrorString(e));
+  return KDLAE_OK;
+}
+
+extern "C" int kdlae_debug_bn(const kdlae_debug_bn_desc* d, void* stream) {
+  if (!d) return fail(KDLAE_EINVAL_CONFIG, "null descriptor");
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e;
+  const bool need_part = d->op == 0 || d->op == 2;
+  if (need_part && (!d->part || d->part_floats < tr::bn_part_floats(d->C)))
+    return fail(KDLAE_EINVAL_CONFIG, "part must hold 2048 C floats");
+  switch (d->op) {
+    case 0:
+      e = tr::launch_bn_stats(d->x, d->ldx, d->C, d->P, d->mean, d->rstd, d->running_mean, d->running_var, d->momentum,
+                              d->part, s);
+      break;
+    case 1:
+      e = tr::launch_bn_apply_relu(d->x, d->ldx, d->mean, d->rstd, d->gamma, d->beta, d->C, d->P, d->out, d->ldo, s);
+      break;
+    case 2:
+      e = tr::launch_bn_bwd_reduce(d->dy, d->ldd, d->y, d->ldy, d->x, d->ldx, d->mean, d->rstd, d->C, d->P, d->dgamma,
+                                   d->dbeta, d->part, s);
+      break;
+    case 3:
+      e = tr::launch_bn_bwd_dx(d->dy, d->ldd, d->y, d->ldy, d->x, d->ldx, d->mean, d->rstd, d->gamma, d->dgamma,
+                               d->dbeta, d->C, d->P, d->out, d->ldo, s);
+      break;
+    case 4: e = tr::launch_upsample2x_bwd(d->x, d->ldx, d->out, d->ldo, d->C, d->N, d->h, d->w, s); break;
+    case 5:
+      if (!d->x || !d->out || d->N < 1 || d->h < 1 || d->w < 1 || d->ldx < d->C || d->ldo < d->C)
+        return fail(KDLAE_EINVAL_SHAPE, "bad upsample geometry");
+      e = kdlae::launch_upsample2x(d->x, d->ldx, d->out, d->ldo, d->C, d->N, d->h, d->w, s);
+      break;
+    default: return fail(KDLAE_EINVAL_CONFIG, "op must be 0..5");
+  }
+  if (e != hipSuccess) return fail(KDLAE_EHIP, std::string("kdlae_debug_bn: ") + hipGetErrorString(e));
   return KDLAE_OK;
 }

@@ -28,7 +28,8 @@ from . import _lib
 
 __all__ = ["TrainEngine", "TeacherTrainFn", "L1LossSr", "KDLAETrainer", "MixingAugment", "sync_gradients",
            "grad_buckets", "sync_gradients_bucketed", "StudentTrainEngine", "StudentTrainFn",
-           "L1LossForVideoFrames", "KDLAESTrainer"]
+           "L1LossForVideoFrames", "KDLAESTrainer", "AsdqeTrainEngine", "AsdqeTrainFn", "asdqe_train_forward",
+           "asdqe_dropout_masks", "ASDQETrainer"]
 
 
 def _vp(t):
@@ -465,6 +466,287 @@ class KDLAESTrainer:
 
     def grad_norm(self) -> torch.Tensor:
         return self._opt_scratch[2048]
+
+
+# ------------------------------------------------------------------ ASDQE (Train/ASDQE.py)
+def _bn_modules(model):
+    return [m for m in model.modules() if isinstance(m, torch.nn.BatchNorm2d)]
+
+
+def asdqe_dropout_masks(B, device, generator=None):
+    """The regressor's two Dropout masks (p = 0.5 / 0.3, ASDQE_model.py:148,151), already scaled: 0 or
+    1 / (1 - p), [B, 256] and [B, 64].  Drawn on the device with ``torch.rand(generator=...)``: NOT the
+    bits ``nn.Dropout`` would draw from torch's global stream."""
+    m1 = (torch.rand(B, 256, device=device, generator=generator) >= 0.5).to(torch.float32) * 2.0
+    m2 = (torch.rand(B, 64, device=device, generator=generator) >= 0.3).to(torch.float32) * (1.0 / 0.7)
+    return m1, m2
+
+
+class AsdqeTrainEngine:
+    """``asdqe_train_*`` handle for one DenoiseRatePredictor config on one device (ASDQE_model.py:123-171
+    in train mode: batch-statistics BatchNorm with the running update, Dropout by explicit masks)."""
+
+    def __init__(self, model, device: torch.device):
+        L = _lib.lib()
+        self.device = device
+        h = ctypes.c_void_p()
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        _lib.check(L.asdqe_train_create(ctypes.byref(model._c_config()), idx, ctypes.byref(h)), "asdqe_train_create")
+        self.handle = h
+        self._L = L
+        self._dtor = L.asdqe_train_destroy
+        self.keys = []
+        for i in range(L.asdqe_train_num_params(h)):
+            name, numel, off = ctypes.c_char_p(), ctypes.c_int64(), ctypes.c_int64()
+            _lib.check(L.asdqe_train_param_info(h, i, ctypes.byref(name), ctypes.byref(numel), ctypes.byref(off)),
+                       "asdqe_train_param_info")
+            self.keys.append((name.value.decode(), int(numel.value), int(off.value)))
+        self.numel = int(L.asdqe_train_num_floats(h))
+        self.num_stats = int(L.asdqe_train_num_stat_floats(h))
+        self.in_channels = int(model._cfg["in_channels"])
+        if [k for k, _, _ in self.keys] != [k for k, _ in model.named_parameters()]:
+            raise RuntimeError("DenoiseRatePredictor parameters do not match the training handle's layout")
+        # per BatchNorm2d, in state_dict order: [running_mean | running_var] at this offset
+        self.stat_slots, off = [], 0
+        for bn in _bn_modules(model):
+            self.stat_slots.append((off, bn.num_features))
+            off += 2 * bn.num_features
+        if off != self.num_stats:
+            raise RuntimeError("DenoiseRatePredictor BatchNorm buffers do not match the training handle's layout")
+        self.ws = None
+        self.generation = 0
+
+    def __del__(self):
+        try:
+            if self.handle:
+                self._dtor(self.handle)
+        except Exception:
+            pass
+
+    def used_ranges(self):
+        return [[0, self.numel]]
+
+    flatten = TrainEngine.flatten
+    packed = TrainEngine.packed
+
+    def flatten_stats(self, model) -> torch.Tensor:
+        bns = _bn_modules(model)
+        flat = torch.empty(self.num_stats, dtype=torch.float32, device=self.device)
+        for (off, c), bn in zip(self.stat_slots, bns):
+            flat[off:off + c] = bn.running_mean.detach().to(torch.float32)
+            flat[off + c:off + 2 * c] = bn.running_var.detach().to(torch.float32)
+        return flat
+
+    def forward(self, theta, stats, lq, gt, mask1=None, mask2=None):
+        """Train-mode forward with activations kept for ``backward``; ``stats`` is updated in place."""
+        if lq.device.type != "cuda" or gt.device != lq.device:
+            raise RuntimeError("ASDQE training runs on ROCm devices only; there is no CPU fallback")
+        ci = self.in_channels  # the kernels index the images with the handle's channel count
+        if lq.dim() != 4 or lq.shape[1] != ci or lq.shape != gt.shape:
+            raise RuntimeError(f"expected lq, gt [B,{ci},H,W] of equal shape, got {tuple(lq.shape)}, {tuple(gt.shape)}")
+        lq = lq.detach().to(torch.float32).contiguous()
+        gt = gt.detach().to(torch.float32).contiguous()
+        B, _, H, W = lq.shape
+        for m, n in ((mask1, 256), (mask2, 64)):
+            if m is not None and (tuple(m.shape) != (B, n) or m.device != lq.device):
+                raise RuntimeError(f"dropout mask must be a [{B}, {n}] tensor on {lq.device}")
+        mask1 = mask1.detach().to(torch.float32).contiguous() if mask1 is not None else None
+        mask2 = mask2.detach().to(torch.float32).contiguous() if mask2 is not None else None
+        nbytes = int(self._L.asdqe_train_workspace_bytes(self.handle, B, H, W))
+        if nbytes < 0:
+            _lib.check(1, "asdqe_train_workspace_bytes")
+        if self.ws is None or self.ws.numel() < nbytes:
+            self.ws = None
+            self.ws = torch.empty(nbytes, dtype=torch.uint8, device=lq.device)
+        score = torch.empty((B, 1), dtype=torch.float32, device=lq.device)
+        rc = self._L.asdqe_train_forward(self.handle, _vp(theta), _vp(stats), _vp(lq), _vp(gt), B, H, W, _vp(mask1),
+                                         _vp(mask2), _vp(score), _vp(self.ws), self.ws.numel(), _stream(lq.device))
+        _lib.check(rc, "asdqe_train_forward")
+        self.generation += 1
+        return score
+
+    def backward(self, theta, dscore, grad, accumulate=False):
+        if self.ws is None:
+            raise RuntimeError("ASDQE training: backward without a preceding forward")
+        dscore = dscore.detach().to(torch.float32).contiguous()
+        rc = self._L.asdqe_train_backward(self.handle, _vp(theta), _vp(dscore), _vp(grad), 1 if accumulate else 0,
+                                          _vp(self.ws), self.ws.numel(), _stream(grad.device))
+        _lib.check(rc, "asdqe_train_backward")
+        return grad
+
+
+class AsdqeTrainFn(torch.autograd.Function):
+    """Autograd node for one train-mode DenoiseRatePredictor forward (the images get no gradient)."""
+
+    @staticmethod
+    def forward(ctx, engine, stats, lq, gt, mask1, mask2, *params):
+        theta = engine.flatten(params)
+        score = engine.forward(theta, stats, lq, gt, mask1, mask2)
+        ctx.engine = engine
+        ctx.generation = engine.generation
+        ctx.theta = theta
+        ctx.shapes = [p.shape for p in params]
+        return score
+
+    @staticmethod
+    def backward(ctx, dscore):
+        eng = ctx.engine
+        if eng.generation != ctx.generation:
+            raise RuntimeError("DenoiseRatePredictor: a second training forward ran before this graph's backward; "
+                               "the HIP engine keeps one set of saved activations per model and device")
+        grad = torch.empty(eng.numel, dtype=torch.float32, device=ctx.theta.device)
+        eng.backward(ctx.theta, dscore, grad)
+        return (None, None, None, None, None, None,
+                *[grad[off:off + n].view(shape) for (k, n, off), shape in zip(eng.keys, ctx.shapes)])
+
+
+def _asdqe_engine(model, device):
+    engines = model.__dict__.setdefault("_train_engines", {})
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    eng = engines.get(idx)
+    if eng is None:
+        eng = engines[idx] = AsdqeTrainEngine(model, torch.device("cuda", idx))
+    return eng
+
+
+def asdqe_train_forward(model, lq, gt, masks=None, generator=None):
+    """``model(lq, gt)`` as ``model.train()`` computes it in the reference (batch-statistics BatchNorm,
+    Dropout), on the HIP path, for users who write their own loop: the returned score [B, 1] carries an
+    autograd graph into ``model.parameters()``, so ``loss.backward()`` and any torch optimizer work.
+    The BatchNorm buffers are updated as ``nn.BatchNorm2d`` updates them (momentum 0.1, unbiased running
+    variance, ``num_batches_tracked += 1``).  One forward per backward: the engine keeps one set of saved
+    activations per model and device, and a second training forward before the first graph's backward
+    raises at that backward.
+
+    ``masks=(mask1 [B, 256], mask2 [B, 64])`` fixes the two Dropout masks (values 0 or 1 / (1 - p);
+    ``None`` entries = no dropout); by default they are drawn with ``asdqe_dropout_masks(generator=...)``,
+    which are not the bits ``nn.Dropout`` would draw from torch's global stream.  fp32 throughout."""
+    if lq.device.type != "cuda":
+        raise RuntimeError("ASDQE training runs on ROCm devices only; there is no CPU fallback")
+    eng = _asdqe_engine(model, lq.device)
+    m1, m2 = masks if masks is not None else asdqe_dropout_masks(lq.shape[0], lq.device, generator)
+    stats = eng.flatten_stats(model)
+    score = AsdqeTrainFn.apply(eng, stats, lq, gt, m1, m2, *model.parameters())
+    with torch.no_grad():
+        for (off, c), bn in zip(eng.stat_slots, _bn_modules(model)):
+            bn.running_mean.copy_(stats[off:off + c])
+            bn.running_var.copy_(stats[off + c:off + 2 * c])
+            bn.num_batches_tracked += 1
+    return score
+
+
+class ASDQETrainer:
+    """``train_epoch``'s inner loop (Train/ASDQE.py:95-122) on flat buffers: train-mode forward, MSE /
+    ``accumulation_steps``, backward accumulating into ``grad``, and every ``accumulation_steps``-th
+    micro-batch one Adam step (``kdlae_train_clip_adamw`` without clipping; with ``weight_decay=0`` that is
+    ``torch.optim.Adam``) followed by zeroing the gradient.  The model's parameters and BatchNorm buffers
+    become views of the trainer's flat buffers, so ``model.state_dict()`` (what ``torch.save`` writes at
+    :210 and ASDQE_test.py:79 loads) and the eval forward always see the trained values.
+
+    fp32 throughout: the reference's ``autocast`` + ``GradScaler`` (fp16 on CUDA) is not needed and this
+    path is not narrower arithmetic.  Dropout masks come from ``asdqe_dropout_masks`` with a generator
+    seeded by ``seed`` (not the bits ``nn.Dropout`` would draw).  ``lr`` is a plain attribute: drive it
+    with any plateau rule."""
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, accumulation_steps=32,
+                 group=None, seed=None):
+        params = list(model.parameters())
+        if not params or params[0].device.type != "cuda":
+            raise RuntimeError("ASDQETrainer: move the model to a ROCm device first (no CPU fallback)")
+        if accumulation_steps < 1:
+            raise ValueError("accumulation_steps must be >= 1")
+        dev = params[0].device
+        self.model = model
+        self.engine = eng = _asdqe_engine(model, dev)
+        self.theta = eng.flatten(params).contiguous()
+        self.stats = eng.flatten_stats(model)
+        with torch.no_grad():
+            for (k, n, off), p in zip(eng.keys, params):
+                p.data = self.theta[off:off + n].view(p.shape)
+            for (off, c), bn in zip(eng.stat_slots, _bn_modules(model)):
+                bn.running_mean.data = self.stats[off:off + c]
+                bn.running_var.data = self.stats[off + c:off + 2 * c]
+        self.grad = torch.zeros(eng.numel, dtype=torch.float32, device=dev)
+        self.exp_avg = torch.zeros_like(self.grad)
+        self.exp_avg_sq = torch.zeros_like(self.grad)
+        self.lr, self.betas, self.eps, self.weight_decay = lr, tuple(betas), eps, weight_decay
+        self.accumulation_steps = int(accumulation_steps)
+        self.group = group
+        self.step_count = 0
+        self.micro = 0  # micro-batches accumulated since the last step
+        self.generator = torch.Generator(device=dev)
+        if seed is not None:
+            self.generator.manual_seed(int(seed))
+        L = _lib.lib()
+        self._opt_scratch = torch.empty(int(L.kdlae_train_adamw_scratch_floats()), dtype=torch.float32, device=dev)
+        self._loss = torch.zeros(2, dtype=torch.float32, device=dev)
+
+    def _target(self, target, B, dev):
+        t = target.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        if t.numel() != B:
+            raise ValueError(f"target has {t.numel()} scores for a batch of {B}")
+        return t
+
+    def train_batch(self, lq, gt, target, masks=None):
+        """One micro-batch: returns ``(loss * accumulation_steps, mae)`` as the reference logs them, i.e.
+        the unscaled MSE and the mean absolute error, as 0-d device tensors."""
+        eng, L = self.engine, _lib.lib()
+        if lq.device.type != "cuda" or gt.device != lq.device:
+            raise RuntimeError("ASDQE training runs on ROCm devices only; there is no CPU fallback")
+        self.model.train()
+        m1, m2 = masks if masks is not None else asdqe_dropout_masks(lq.shape[0], lq.device, self.generator)
+        score = eng.forward(self.theta, self.stats, lq, gt, m1, m2)
+        with torch.no_grad():
+            for bn in _bn_modules(self.model):
+                bn.num_batches_tracked += 1
+        B = score.shape[0]
+        t = self._target(target, B, score.device)
+        dscore = torch.empty_like(score)
+        loss = torch.empty(2, dtype=torch.float32, device=score.device)
+        rc = L.kdlae_train_mse(_vp(score), _vp(t), B, 1.0 / self.accumulation_steps, _vp(dscore), _vp(loss),
+                               _stream(score.device))
+        _lib.check(rc, "kdlae_train_mse")
+        eng.backward(self.theta, dscore, self.grad, accumulate=True)
+        self.score = score
+        self.micro += 1
+        if self.micro == self.accumulation_steps:
+            self.step()
+        return loss[0], loss[1]
+
+    def step(self):
+        """Adam on the accumulated gradient (all-reduced over ``group`` first), then ``grad = 0``."""
+        gscale = sync_gradients(self.grad, self.group)
+        self.step_count += 1
+        b1, b2 = self.betas
+        rc = _lib.lib().kdlae_train_clip_adamw(
+            _vp(self.theta), _vp(self.grad), _vp(self.exp_avg), _vp(self.exp_avg_sq), self.engine.numel,
+            float(gscale), 0.0, float(self.lr), float(b1), float(b2), float(self.eps), float(self.weight_decay),
+            self.step_count, None, 0, _vp(self._opt_scratch), _stream(self.theta.device))
+        _lib.check(rc, "kdlae_train_clip_adamw")
+        self.grad.zero_()
+        self.micro = 0
+
+    def flush(self):
+        """Step on a partial accumulation window (the reference's ``len(loader) % accumulation_steps``
+        tail, Train/ASDQE.py:114-118); a no-op when nothing is accumulated."""
+        if self.micro:
+            self.step()
+
+    @torch.no_grad()
+    def validate_batch(self, lq, gt, target):
+        """The validation pass (Train/ASDQE.py:124-146): the eval HIP forward; returns ``(mse, mae)``."""
+        was = self.model.training
+        self.model.eval()
+        try:
+            score = self.model(lq, gt)
+        finally:
+            self.model.train(was)
+        t = self._target(target, score.shape[0], score.device).view_as(score)
+        d = score - t
+        return (d * d).mean(), d.abs().mean()
+
+    def state_dict(self):
+        return self.model.state_dict()
 
 
 def _mix(t, perm, lam):
