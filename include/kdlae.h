@@ -396,6 +396,24 @@ int asdqe_train_backward(asdqe_train_handle* h, const float* theta, const float*
 int kdlae_train_mse(const float* score, const float* target, int n, float scale, float* dscore, float* loss,
                     void* stream);
 
+/* ---- Validation metric (metrics.hip).  Replaces the two reductions of calculate_psnr
+ * (Train/basicsr/metrics/psnr_ssim.py:53-70) over contiguous fp32 device tensors pred [B, C, Hs, Ws] and
+ * gt [B, C, Hg, Wg]: the compared region is the top-left h x w window of both (pad_test's crop,
+ * image_restoration_model.py:236-237, so neither the padded output nor the unpadded target needs a copy)
+ * minus crop_border pixels on all four sides (:58-60).
+ *   mode 0: the floats as they are (val.use_image: false, every yml under paper202508/);
+ *   mode 1: both operands through tensor2img's uint8 route first (img_util.py:67-68,91-94: clamp to
+ *           [0, 1], * 255 in fp32, round half to even), compared on the 0..255 scale.
+ * out [B][2] (device, fp64): out[b][0] = sum of (pred - gt)^2 over image b's region, out[b][1] = max of pred
+ * over it (after the quantisation in mode 1; psnr_ssim.py:69 looks at the first operand only).  fp64
+ * accumulation in a fixed two-stage order without atomics: equal inputs give equal bits.  The host
+ * finishes: mse = sse / n, inf when 0, else 20 log10((max <= 1 ? 1 : 255) / sqrt(mse)).  Nothing here
+ * synchronises; the result stays on the device.  2 crop_border >= h or w: KDLAE_EINVAL_SHAPE.
+ * scratch: device buffer of kdlae_metric_scratch_bytes() bytes (8-byte aligned). */
+int64_t kdlae_metric_scratch_bytes(void);
+int kdlae_metric_psnr(const float* pred, const float* gt, int B, int C, int Hs, int Ws, int Hg, int Wg, int h, int w,
+                      int crop_border, int mode, double* out, void* scratch, void* stream);
+
 /* ---- Kernel self-test entry points (tests/test_kernel_variants_gpu.py; not part of the drop-in
  * boundary).  One launch of the training GEMM family on caller device buffers:
  *   C(m, n) = sum_k A(m, k) B(k, n) [+ bias[n]] [+ rs[n] R(m, n)], batch z = z1 * nz2 + z2, every

@@ -181,6 +181,16 @@ class _Engine:
             self.handle, ctypes.c_void_p(self.flat.data_ptr()), self.numel, ctypes.c_void_p(stream)),
             self.prefix + "_pack_device")
 
+    def pack_flat(self, flat: torch.Tensor, stream) -> None:
+        """Pack a caller-owned flat parameter vector (every key back to back in ``self.keys`` order, fp32)
+        instead of the module's live parameters: how a trainer evaluates its EMA weights."""
+        if flat.dtype != torch.float32 or flat.numel() != self.numel or not flat.is_contiguous() or \
+                flat.device != torch.device("cuda", self.device_index):
+            raise RuntimeError(f"expected a contiguous fp32 vector of {self.numel} parameters on cuda:{self.device_index}")
+        _lib.check(getattr(_lib.lib(), self.prefix + "_pack_device")(
+            self.handle, ctypes.c_void_p(flat.data_ptr()), self.numel, ctypes.c_void_p(stream)),
+            self.prefix + "_pack_device")
+
     def workspace(self, nbytes: int, device) -> torch.Tensor:
         if self.ws is None or self.ws.numel() < nbytes:
             self.ws = None
@@ -359,14 +369,18 @@ class KDLAE_teacher(nn.Module):
         g.replay()
         return {k: (v.clone() if v is not None else None) for k, v in s_out.items()}
 
-    def _forward_eager(self, img, rate):
+    def _forward_eager(self, img, rate, flat=None):
+        """``flat``: run with this packed parameter vector (``_Engine.pack_flat``) instead of the module's own."""
         dev = img.device
         B, _, H, W = img.shape
         cat = rate is not None
         denoise_rate = rate
         stream = torch.cuda.current_stream(dev).cuda_stream
         eng = self.engine(dev)
-        eng.sync_params(self, stream)
+        if flat is None:
+            eng.sync_params(self, stream)
+        else:
+            eng.pack_flat(flat, stream)
         img_c = img.detach().to(torch.float32).contiguous()
         rate_c = denoise_rate.detach().to(device=dev, dtype=torch.float32).contiguous() if cat else None
         oc = self._cfg["out_channels"]
@@ -474,10 +488,18 @@ class KDLAE_student(nn.Module):
                 warnings.warn("KDLAE_student in eval mode with grad enabled: the HIP inference path returns "
                               "outputs without an autograd graph")
                 self._warned_grad = True
+        return self._forward_eager(x)
+
+    def _forward_eager(self, x, flat=None):
+        """``flat``: run with this packed parameter vector (``_Engine.pack_flat``) instead of the module's own."""
+        B, Fr, H, W = x.shape
         dev = x.device
         stream = torch.cuda.current_stream(dev).cuda_stream
         eng = self.engine(dev)
-        eng.sync_params(self, stream)
+        if flat is None:
+            eng.sync_params(self, stream)
+        else:
+            eng.pack_flat(flat, stream)
         x_c = x.detach().to(torch.float32).contiguous()
         out = torch.empty((B, Fr, H, W), device=dev, dtype=torch.float32)
         L = _lib.lib()

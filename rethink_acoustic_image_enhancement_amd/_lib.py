@@ -51,6 +51,7 @@ EXPORTS = (
     "asdqe_train_num_floats", "asdqe_train_num_stat_floats", "asdqe_train_workspace_bytes", "asdqe_train_forward",
     "asdqe_train_backward", "kdlae_train_mse",
     "kdlae_debug_bn",
+    "kdlae_metric_scratch_bytes", "kdlae_metric_psnr",
 )
 
 
@@ -208,13 +209,17 @@ def lib() -> ctypes.CDLL:
     L.asdqe_train_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p]
     L.kdlae_train_mse.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_float, c_void_p, c_void_p, c_void_p]
     L.kdlae_debug_bn.argtypes = [c_void_p, c_void_p]
+    L.kdlae_metric_scratch_bytes.argtypes = []
+    L.kdlae_metric_scratch_bytes.restype = c_int64
+    L.kdlae_metric_psnr.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                    c_int, c_int, c_void_p, c_void_p, c_void_p]
     L.kdlae_debug_tgemm.argtypes = [c_void_p, c_void_p]
     for f in ("kdlae_debug_gemm", "kdlae_debug_gram", "kdlae_debug_ln", "kdlae_debug_small_in"):
         getattr(L, f).argtypes = [c_void_p, c_void_p]
     L.kdlae_debug_gemm_variant.argtypes = [c_int, c_int, ctypes.POINTER(c_int)]
     for name in EXPORTS:
         if not name.endswith(("_last_error", "_abi_version", "_workspace_bytes", "_padded_size", "_num_floats",
-                              "_scratch_floats", "_params_numel", "_mark_lo", "_num_stat_floats")):
+                              "_scratch_floats", "_scratch_bytes", "_params_numel", "_mark_lo", "_num_stat_floats")):
             getattr(L, name).restype = c_int
     _lib = L
     return L

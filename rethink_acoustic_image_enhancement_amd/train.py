@@ -29,7 +29,7 @@ from . import _lib
 __all__ = ["TrainEngine", "TeacherTrainFn", "L1LossSr", "KDLAETrainer", "MixingAugment", "sync_gradients",
            "grad_buckets", "sync_gradients_bucketed", "StudentTrainEngine", "StudentTrainFn",
            "L1LossForVideoFrames", "KDLAESTrainer", "AsdqeTrainEngine", "AsdqeTrainFn", "asdqe_train_forward",
-           "asdqe_dropout_masks", "ASDQETrainer"]
+           "asdqe_dropout_masks", "ASDQETrainer", "flat_to_optim_state", "optim_state_to_flat"]
 
 
 def _vp(t):
@@ -38,6 +38,144 @@ def _vp(t):
 
 def _stream(dev):
     return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+# ------------------------------------------------------------------ training state (BaseModel.save_training_state)
+def _group_template(hyper):
+    """The one ``param_groups`` entry this torch writes for AdamW (Adam when ``hyper['optimizer'] == 'Adam'``),
+    taken from a throw-away optimizer so every key this torch version knows is there with its default."""
+    cls = torch.optim.Adam if hyper.get("optimizer", "AdamW") == "Adam" else torch.optim.AdamW
+    opt = cls([torch.nn.Parameter(torch.zeros(1))], lr=float(hyper["lr"]), betas=tuple(hyper["betas"]),
+              eps=float(hyper["eps"]), weight_decay=float(hyper["weight_decay"]), amsgrad=False)
+    return opt.state_dict()["param_groups"][0]
+
+
+def flat_to_optim_state(keys, exp_avg, exp_avg_sq, step, hyper, shapes=None) -> dict:
+    """The trainers' flat AdamW moments as ``torch.optim.AdamW(...).state_dict()`` (what
+    BaseModel.save_training_state stores under ``'optimizers'``, Train/basicsr/models/base_model.py:311-330).
+
+    ``keys``: the engine's ``(name, numel, offset)`` list in ``model.parameters()`` order, the order BasicSR
+    hands to the optimizer, so parameter i of the dict is ``keys[i]``.  ``shapes``: the parameters' shapes
+    (default: flat ``[numel]``).  ``hyper``: ``lr, betas, eps, weight_decay`` (+ ``optimizer='Adam'`` for the
+    Adam layout).  ``state[i] = {'step', 'exp_avg', 'exp_avg_sq'}`` with copies of the moments; one param group."""
+    state = {}
+    for i, (_, n, off) in enumerate(keys):
+        shape = tuple(shapes[i]) if shapes is not None else (n,)
+        state[i] = {"step": torch.tensor(float(int(step)), dtype=torch.float32),
+                    "exp_avg": exp_avg[off:off + n].detach().clone().view(shape),
+                    "exp_avg_sq": exp_avg_sq[off:off + n].detach().clone().view(shape)}
+    group = _group_template(hyper)
+    group["params"] = list(range(len(keys)))
+    return {"state": state, "param_groups": [group]}
+
+
+def optim_state_to_flat(state, keys, out_exp_avg, out_exp_avg_sq, shapes=None) -> int:
+    """Inverse of ``flat_to_optim_state``: an AdamW / Adam ``state_dict()`` (from here or from stock PyTorch)
+    into the flat moment buffers; returns the step count.  The pad floats between the 16-byte-aligned keys
+    are zeroed.  A parameter torch holds no state for (its ``.grad`` was always None) gets zero moments.
+    Raises ValueError on more than one param group, ``amsgrad=True``, a wrong number of parameters, a shape
+    (or element count) mismatch at any index, or parameters at different steps."""
+    groups = state.get("param_groups", [])
+    if len(groups) != 1:
+        raise ValueError(f"expected an optimizer state with one param group, got {len(groups)}")
+    group = groups[0]
+    if group.get("amsgrad", False):
+        raise ValueError("amsgrad=True optimizer state cannot be resumed: the HIP AdamW keeps no max_exp_avg_sq")
+    params = list(group["params"])
+    if len(params) != len(keys):
+        raise ValueError(f"optimizer state has {len(params)} parameters, the model has {len(keys)}")
+    st = state.get("state", {})
+    for i, (pid, (name, n, off)) in enumerate(zip(params, keys)):
+        ent = st.get(pid)
+        if ent is None:
+            continue
+        want = tuple(shapes[i]) if shapes is not None else None
+        for k in ("exp_avg", "exp_avg_sq"):
+            t = ent[k]
+            if t.numel() != n or (want is not None and tuple(t.shape) != want):
+                raise ValueError(f"parameter {i} ({name}): {k} has shape {tuple(t.shape)}, expected "
+                                 f"{want if want is not None else (n,)}")
+    steps = {int(float(st[pid]["step"])) for pid in params if pid in st}
+    if len(steps) > 1:
+        raise ValueError(f"parameters are at different steps {sorted(steps)}: the HIP AdamW keeps one step count")
+    out_exp_avg.zero_()
+    out_exp_avg_sq.zero_()
+    for pid, (name, n, off) in zip(params, keys):
+        ent = st.get(pid)
+        if ent is None:
+            continue
+        out_exp_avg[off:off + n].copy_(ent["exp_avg"].detach().reshape(-1))
+        out_exp_avg_sq[off:off + n].copy_(ent["exp_avg_sq"].detach().reshape(-1))
+    return steps.pop() if steps else 0
+
+
+class _TrainingState:
+    """``BaseModel.save_training_state`` / ``resume_training`` (base_model.py:311-351) for the flat-buffer
+    trainers: ``{'epoch', 'iter', 'optimizers': [AdamW state_dict], 'schedulers': [...]}``.  The network
+    weights travel separately (``model.state_dict()`` / checkpoint.py), as in BasicSR."""
+
+    _optimizer_name = "AdamW"
+
+    def _hyper(self):
+        return dict(lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay,
+                    optimizer=self._optimizer_name)
+
+    def _shapes(self):
+        return [tuple(p.shape) for p in self.model.parameters()]
+
+    def training_state(self, epoch: int, current_iter: int) -> dict:
+        """The dict ``torch.save`` writes as ``{current_iter}.state``.  Call it after iteration
+        ``current_iter``'s ``optimize_parameters``; it copies the moments (later steps do not change it)."""
+        opt = flat_to_optim_state(self.engine.keys, self.exp_avg, self.exp_avg_sq, self.step_count, self._hyper(),
+                                  self._shapes())
+        scheds = []
+        if getattr(self, "scheduler", None) is not None:
+            # BaseModel.update_learning_rate steps the scheduler from iteration 2 on (:186-188)
+            scheds.append({"last_epoch": max(int(current_iter) - 1, 0)})
+            opt["param_groups"][0]["initial_lr"] = self.init_lr   # what a torch scheduler adds to its group
+        return {"epoch": epoch, "iter": current_iter, "optimizers": [opt], "schedulers": scheds}
+
+    def resume_training(self, state: dict) -> None:
+        """Inverse of ``training_state``; also takes a bare ``optimizer.state_dict()`` of stock AdamW / Adam.
+        Restores the moments, the step count, lr and the hyperparameters; with a scheduler set, lr is then
+        re-derived through ``update_learning_rate``.  Load the network weights first (``load_state_dict``)."""
+        if "optimizers" in state:
+            if len(state["optimizers"]) != 1:
+                raise ValueError(f"expected one optimizer in the training state, got {len(state['optimizers'])}")
+            opt = state["optimizers"][0]
+        elif "param_groups" in state:
+            opt = state
+        else:
+            raise ValueError("not a training state: neither 'optimizers' nor 'param_groups'")
+        self.step_count = optim_state_to_flat(opt, self.engine.keys, self.exp_avg, self.exp_avg_sq, self._shapes())
+        g = opt["param_groups"][0]
+        self.lr, self.betas = float(g["lr"]), tuple(float(b) for b in g["betas"])
+        self.eps, self.weight_decay = float(g["eps"]), float(g["weight_decay"])
+        if hasattr(self, "init_lr"):
+            self.init_lr = float(g.get("initial_lr", self.init_lr))
+        scheds = state.get("schedulers", [])
+        if getattr(self, "scheduler", None) is not None and scheds:
+            self.update_learning_rate(int(scheds[0]["last_epoch"]) + 1)
+
+
+def _inference_flat(trainer, vec):
+    """``vec`` (theta or theta_ema, the training handle's aligned layout) as the flat vector the module's
+    inference handle packs from: every key back to back in state_dict order."""
+    dev = vec.device
+    infer_keys = [k for k, _ in trainer.model.engine(dev).keys]
+    if infer_keys != [k for k, _, _ in trainer.engine.keys]:
+        raise RuntimeError("the inference handle's state_dict layout differs from the training handle's")
+    return trainer.engine.packed(vec)
+
+
+def _reflect_pad(t, multiple):
+    """pad_test (image_restoration_model.py:226-234): reflect-pad right and bottom to a multiple."""
+    h, w = t.shape[-2:]
+    ph = (multiple - h % multiple) % multiple if multiple else 0
+    pw = (multiple - w % multiple) % multiple if multiple else 0
+    if ph or pw:
+        t = torch.nn.functional.pad(t, (0, pw, 0, ph), "reflect")
+    return t
 
 
 class TrainEngine:
@@ -386,7 +524,7 @@ class L1LossForVideoFrames(torch.nn.Module):
                                  0 if self.reduction == "mean" else 1)
 
 
-class KDLAESTrainer:
+class KDLAESTrainer(_TrainingState):
     """ImageCleanModel.optimize_parameters for KDLAE_student with KDLAES.yml (AdamW lr 3e-4 wd 1e-4 betas
     (0.9, 0.999); use_grad_clip -> clip_grad_norm_(0.01); L1LossForVideoFrames(0.9, mean, temporal 0.1);
     mixup): flat buffers end to end, one RCCL all-reduce of the flat gradient for DDP."""
@@ -466,6 +604,28 @@ class KDLAESTrainer:
 
     def grad_norm(self) -> torch.Tensor:
         return self._opt_scratch[2048]
+
+    @torch.no_grad()
+    def validate(self, batches, window_size=8, crop_border=0, use_image=False):
+        """ImageCleanModel.nondist_validation (image_restoration_model.py:264-348) for ``(lq, gt)`` pairs of
+        [B, F, H, W] tensors: reflect-pad to the multiple the student needs (2^levels, and ``window_size``),
+        the inference engine, PSNR of the top-left H x W window against ``gt``.  Returns ``{'psnr': mean}``
+        over all images.  The trainer's state is untouched."""
+        from .metrics import psnr_batch
+        need = 1 << self.model.num_levels
+        mult = math.lcm(need, int(window_size)) if window_size else need
+        flat = _inference_flat(self, self.theta)
+        vals = []
+        for lq, gt in batches:
+            if lq.device.type != "cuda":
+                raise RuntimeError("KDLAE validation runs on ROCm devices only; there is no CPU fallback")
+            h, w = lq.shape[-2:]
+            out = self.model._forward_eager(_reflect_pad(lq.to(torch.float32), mult), flat=flat)
+            self.val_output = out[..., :h, :w]  # the last item's cropped output (pad_test's self.output)
+            vals.append(psnr_batch(out, gt.to(out.device), (h, w), crop_border, use_image))
+        if not vals:
+            raise ValueError("validate: no batches")
+        return {"psnr": float(torch.cat(vals).mean())}
 
 
 # ------------------------------------------------------------------ ASDQE (Train/ASDQE.py)
@@ -635,7 +795,7 @@ def asdqe_train_forward(model, lq, gt, masks=None, generator=None):
     return score
 
 
-class ASDQETrainer:
+class ASDQETrainer(_TrainingState):
     """``train_epoch``'s inner loop (Train/ASDQE.py:95-122) on flat buffers: train-mode forward, MSE /
     ``accumulation_steps``, backward accumulating into ``grad``, and every ``accumulation_steps``-th
     micro-batch one Adam step (``kdlae_train_clip_adamw`` without clipping; with ``weight_decay=0`` that is
@@ -747,6 +907,35 @@ class ASDQETrainer:
 
     def state_dict(self):
         return self.model.state_dict()
+
+    _optimizer_name = "Adam"
+
+    def training_state(self, epoch: int, current_iter: int) -> dict:
+        """``_TrainingState.training_state`` plus what a bit-identical continuation inside an accumulation
+        window needs, under keys stock BasicSR ignores: ``asdqe_micro``, the partial ``asdqe_grad`` (when
+        ``micro > 0``) and the dropout generator's ``asdqe_generator_state``."""
+        state = super().training_state(epoch, current_iter)
+        state["asdqe_micro"] = int(self.micro)
+        if self.micro > 0:
+            state["asdqe_grad"] = self.grad.detach().clone()
+        state["asdqe_generator_state"] = self.generator.get_state()
+        return state
+
+    def resume_training(self, state: dict) -> None:
+        """Without the extra keys the accumulation window restarts empty and the generator keeps its state."""
+        super().resume_training(state)
+        self.micro = int(state.get("asdqe_micro", 0))
+        if self.micro < 0 or self.micro >= self.accumulation_steps:
+            raise ValueError(f"asdqe_micro {self.micro} does not fit accumulation_steps {self.accumulation_steps}")
+        g = state.get("asdqe_grad")
+        if self.micro > 0:
+            if g is None or g.numel() != self.grad.numel():
+                raise ValueError("asdqe_micro > 0 needs the partial gradient 'asdqe_grad' of the engine's size")
+            self.grad.copy_(g)
+        else:
+            self.grad.zero_()
+        if state.get("asdqe_generator_state") is not None:
+            self.generator.set_state(state["asdqe_generator_state"].cpu())
 
 
 def _mix(t, perm, lam):
@@ -934,7 +1123,7 @@ class CosineAnnealingRestartCyclicLR:
             1 + math.cos(math.pi * ((last_epoch - nearest_restart) / self.periods[idx])))
 
 
-class KDLAETrainer:
+class KDLAETrainer(_TrainingState):
     """ImageCleanModel.optimize_parameters for KDLAE_teacher (image_restoration_model.py:198-218).
 
     Defaults follow Train/Denoising/Options/paper202508/KDLAET.yml: AdamW lr 1e-5,
@@ -1011,6 +1200,66 @@ class KDLAETrainer:
             raise RuntimeError("ema_decay is 0: there is no EMA copy")
         return {k: self.theta_ema[off:off + n].view(p.shape)
                 for (k, n, off), p in zip(self.engine.keys, self.model.parameters())}
+
+    def load_ema_state_dict(self, sd, strict: bool = True):
+        """Counterpart of ``ema_state_dict()``: copy a ``params_ema`` entry (checkpoint.py reads it) into the
+        EMA buffer.  ``strict``: every parameter key must be present with its shape."""
+        if self.theta_ema is None:
+            raise RuntimeError("ema_decay is 0: there is no EMA copy")
+        names = {k for k, _, _ in self.engine.keys}
+        unexpected = [k for k in sd if k not in names]
+        missing = [k for k in names if k not in sd]
+        if strict and (unexpected or missing):
+            raise RuntimeError(f"load_ema_state_dict: missing keys {missing[:4]}, unexpected keys {unexpected[:4]}")
+        with torch.no_grad():
+            for (k, n, off), p in zip(self.engine.keys, self.model.parameters()):
+                if k not in sd:
+                    continue
+                if tuple(sd[k].shape) != tuple(p.shape):
+                    raise RuntimeError(f"size mismatch for {k}: {tuple(sd[k].shape)} vs {tuple(p.shape)}")
+                self.theta_ema[off:off + n].copy_(sd[k].detach().reshape(-1))
+
+    @torch.no_grad()
+    def validate(self, batches, window_size=8, crop_border=0, use_image=False, use_ema=None):
+        """ImageCleanModel.nondist_validation with pad_test (image_restoration_model.py:226-348) over
+        ``(lq, gt)`` pairs, ``lq = {'img', 'denoise_rate'}``, ``gt = {'hq', 'sr'}``: reflect-pad ``img`` and the
+        rate map right and bottom to a multiple of ``window_size``, run the inference engine
+        (``kdlae_t_forward``), and take the PSNR of the top-left h x w window of ``hq`` (2h x 2w of ``sr``)
+        against its target.  Returns ``{'psnr_hq': mean, 'psnr_sr': mean}`` over all images (``psnr_sr`` only
+        when ``static == 'train'``).
+
+        ``use_ema=None``: the EMA weights when ``ema_decay > 0`` (net_g_ema, :242-248), else the live ones.
+        The chosen flat vector is packed straight into the module's inference handle; the trainer's buffers,
+        the training engine and the module's parameters are not written, so training continues bit for bit."""
+        from .metrics import psnr_batch
+        if use_ema is None:
+            use_ema = self.theta_ema is not None
+        if use_ema and self.theta_ema is None:
+            raise RuntimeError("ema_decay is 0: there is no EMA copy to validate")
+        flat = _inference_flat(self, self.theta_ema if use_ema else self.theta)
+        hqs, srs = [], []
+        for lq, gt in batches:
+            img = lq["img"]
+            if img.device.type != "cuda":
+                raise RuntimeError("KDLAE validation runs on ROCm devices only; there is no CPU fallback")
+            h, w = img.shape[-2:]
+            rate = lq.get("denoise_rate") if self.engine.params_cat else None
+            img_p = _reflect_pad(img.to(torch.float32), window_size)
+            rate_p = _reflect_pad(rate.to(device=img.device, dtype=torch.float32), window_size) if rate is not None \
+                else None
+            out = self.model._forward_eager(img_p, rate_p, flat=flat)
+            # the last item's cropped outputs (pad_test's self.output, :236-237), as views
+            self.val_output = {"hq": out["hq"][..., :h, :w],
+                               "sr": out["sr"][..., :2 * h, :2 * w] if out["sr"] is not None else None}
+            hqs.append(psnr_batch(out["hq"], gt["hq"].to(img.device), (h, w), crop_border, use_image))
+            if out["sr"] is not None:
+                srs.append(psnr_batch(out["sr"], gt["sr"].to(img.device), (2 * h, 2 * w), crop_border, use_image))
+        if not hqs:
+            raise ValueError("validate: no batches")
+        res = {"psnr_hq": float(torch.cat(hqs).mean())}
+        if srs:
+            res["psnr_sr"] = float(torch.cat(srs).mean())
+        return res
 
     def _distributed(self) -> bool:
         return dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1
