@@ -414,8 +414,12 @@ int64_t kdlae_metric_scratch_bytes(void);
 int kdlae_metric_psnr(const float* pred, const float* gt, int B, int C, int Hs, int Ws, int Hg, int Wg, int h, int w,
                       int crop_border, int mode, double* out, void* scratch, void* stream);
 
-/* ---- Kernel self-test entry points (tests/test_kernel_variants_gpu.py; not part of the drop-in
- * boundary).  One launch of the training GEMM family on caller device buffers:
+/* ---- Kernel self-test entry points (not part of the drop-in boundary; nothing here is on a forward
+ * or training path).  tests/test_kernel_variants*_gpu.py: kdlae_debug_tgemm, kdlae_debug_gemm,
+ * kdlae_debug_gram, kdlae_debug_ln, kdlae_debug_small_in, kdlae_debug_bn;
+ * tests/test_train_kernels_gpu.py: kdlae_debug_train, kdlae_debug_train_s (the training steps'
+ * non-GEMM kernels).
+ * One launch of the training GEMM family on caller device buffers:
  *   C(m, n) = sum_k A(m, k) B(k, n) [+ bias[n]] [+ rs[n] R(m, n)], batch z = z1 * nz2 + z2, every
  *   operand offset by z1 * b?1 + z2 * b?2 (floats); amode 1 = implicit 3x3 im2col of the NHWC view A
  *   (pixel stride lda, k = tap * Cg + c, dilation dil, zero padding), bmode 1 = the NHWC view B shifted
@@ -542,6 +546,73 @@ typedef struct kdlae_debug_bn_desc {
   float* part; int64_t part_floats;
 } kdlae_debug_bn_desc;
 int kdlae_debug_bn(const kdlae_debug_bn_desc* d, void* stream);
+
+/* Non-GEMM kernels of the KDLAE-T training step (train.hip, train_dwg.hip, train_small.hip; launch
+ * interface and operand meaning: csrc/train_kernels.h), one launch per call on caller buffers
+ * (tests/test_train_kernels_gpu.py).  NHWC views of Bn x H x W pixels at the pixel stride given
+ * beside each pointer; geometry that a kernel cannot take (null operand, ld < width, Ch > 128, a
+ * partial buffer too small, dw3_small_ok false, ...) returns KDLAE_EINVAL_* before any launch.
+ *   op  0 attn_softmax  in0 = G [Bn heads][Ch][Ch], in1 = sumsq [Bn][2 C], w = temp [heads] -> out0 = Attn
+ *   op  1 attn_bwd      + in2 = Attn, in3 = dAttn -> out0 = Mq, out1 = cq, out2 = ck [Bn heads][Ch],
+ *                       out3 = dtemp partials [Bn heads]; Ch <= 127 (its Ch x Ch tile + 4 floats of LDS
+ *                       must fit the 64 KiB a launch gets without opting in to more; the engine stops at 120)
+ *   op  2 dw_fwd        in0 (C channels), w [C][9], bias (or null), flag = flip -> out0
+ *   op  3 dwgate_fwd    in0 = y (2 C channels, C = hid), w [2 C][9], bias -> out0 = g (C), out1 = yd (2 C; or null)
+ *   op  4 dwgate_bwd    in0 = dg, in1 = yd, in2 = y, w -> out0 = dy, part [blocks][10 * 2 C]
+ *   op  5 dwgate_bwd_rc in0 = dg, in1 = y, w, bias -> out0 = dy, part (as op 4)
+ *   op  6 dw_bwd        in0 = dyd, in1 = y (C channels), w -> out0 = dy, part [blocks][10 C]
+ *                       (ops 4-6: blocks = kdlae_debug_train_blocks(0, Bn, H, W, 0))
+ *   op  7 dw3_small     in0 = dY (C2 = Cout), in1 = X (C = Cin), flag = dil, nblk -> part [nblk][Cout Cin 9]
+ *   op  8 colsum        in0 = x [nseg * P rows][ldi0], C = ncols, flag = square, nblk -> part [nseg][nblk][C]
+ *   op  9 part_reduce   in0 = partials [nseg][nblk][pstride (0 = C)] -> out0 [nseg][C] (accumulate, scale)
+ *   op 10 part_reduce_multi  red[0 .. nred) -> red[j].out [ncols]
+ *   op 11 shuffle       flag = dir (0: PixelUnshuffle [Bn, 2H, 2W, C] -> [Bn, H, W, 4 C]; 1: PixelShuffle back)
+ *   op 12 copy_cols     in0 [P][ldi0] -> out0 [P][ldo0], C columns (accumulate), zero_to
+ *   op 13 nchw_to_nhwc  in0 [Bn][C][P] -> out0 [Bn P][ldo0] (accumulate)
+ *   op 14 nhwc_to_nchw  in0 [Bn P][ldi0] (+ in1 = add [Bn][C][P] or null) -> out0 [Bn][C][P]
+ *   op 15 pack_w3       w = OIHW 3x3 weight, C = Cg, C2 = N, flag = mode (2 or 3) -> out0 [9 Cg][N] */
+typedef struct kdlae_debug_train_red {
+  const float* part; float* out;
+  int nblk, ncols, pstride;
+  float scale;
+} kdlae_debug_train_red;
+typedef struct kdlae_debug_train_desc {
+  int op;
+  const float* in[4]; int ldi[4];
+  const float* w; const float* bias;
+  float* out[4]; int ldo[4];
+  float* part; int64_t part_floats;
+  int C, C2, heads, Bn, H, W;
+  int64_t P;
+  int flag, accumulate, zero_to;
+  int nblk, nseg, pstride;
+  float scale;
+  int nred;
+  kdlae_debug_train_red red[8];
+} kdlae_debug_train_desc;
+int kdlae_debug_train(const kdlae_debug_train_desc* d, void* stream);
+/* Partial-buffer sizing of the kernels above: which 0 = spatial blocks of ops 4-6 for an n x a x b
+ * (Bn x H x W) batch; which 1 = blocks op 7 uses for n pixels, Cin = a, Cout = b and a partial buffer
+ * of cap floats.  -1 on bad arguments. */
+int kdlae_debug_train_blocks(int which, int64_t n, int a, int b, int64_t cap);
+
+/* Non-GEMM kernels of the KDLAE-S training step (train_s.hip; csrc/train_s.h) over NDHWC views of
+ * B x F x H x W pixels, one launch per call:
+ *   op 0 im2col3d      in0 = x (C) -> out = Xcol [pixels][27 C]
+ *   op 1 col2im3d      in0 = dcol [pixels][27 C] -> out = dx (C % 4 == 0, ldo % 4 == 0, 16-byte aligned; accumulate)
+ *   op 2 wperm         in0 [O][C][27] -> out [O][27][C] (dir 0) or back (dir 1)
+ *   op 3 relu_mask     out = dy (in place) *= (in0 = y > 0)
+ *   op 4 maxpool2_bwd  in0 = the pool's input [B, F, 2H, 2W], in1 = dout [B, F, H, W], in2 = dskip (or null) -> out = din
+ *   op 5 upshuffle_add in0 = U [B, F, H/2, W/2] (4 C), in1 = skip [B, F, H, W], bias (or null) -> out = D */
+typedef struct kdlae_debug_train_s_desc {
+  int op;
+  const float* in[3]; int ldi[3];
+  const float* bias;
+  float* out; int ldo;
+  int C, O, B, F, H, W;
+  int accumulate, dir;
+} kdlae_debug_train_s_desc;
+int kdlae_debug_train_s(const kdlae_debug_train_s_desc* d, void* stream);
 
 #ifdef __cplusplus
 }

@@ -52,6 +52,7 @@ EXPORTS = (
     "asdqe_train_backward", "kdlae_train_mse",
     "kdlae_debug_bn",
     "kdlae_metric_scratch_bytes", "kdlae_metric_psnr",
+    "kdlae_debug_train", "kdlae_debug_train_blocks", "kdlae_debug_train_s",
 )
 
 
@@ -79,6 +80,33 @@ class AConfig(ctypes.Structure):
     """asdqe_config (include/kdlae.h) = DenoiseRatePredictor ctor kwargs (ASDQE_model.py:127)."""
 
     _fields_ = [("in_channels", c_int), ("dim", c_int)]
+
+
+class TrainRedDesc(ctypes.Structure):
+    """kdlae_debug_train_red (include/kdlae.h)."""
+
+    _fields_ = [("part", c_void_p), ("out", c_void_p), ("nblk", c_int), ("ncols", c_int), ("pstride", c_int),
+                ("scale", ctypes.c_float)]
+
+
+class TrainDesc(ctypes.Structure):
+    """kdlae_debug_train_desc (include/kdlae.h): the C field `in` is `inp` here."""
+
+    _fields_ = [("op", c_int), ("inp", c_void_p * 4), ("ldi", c_int * 4), ("w", c_void_p), ("bias", c_void_p),
+                ("out", c_void_p * 4), ("ldo", c_int * 4), ("part", c_void_p), ("part_floats", c_int64),
+                ("C", c_int), ("C2", c_int), ("heads", c_int), ("Bn", c_int), ("H", c_int), ("W", c_int),
+                ("P", c_int64), ("flag", c_int), ("accumulate", c_int), ("zero_to", c_int),
+                ("nblk", c_int), ("nseg", c_int), ("pstride", c_int), ("scale", ctypes.c_float),
+                ("nred", c_int), ("red", TrainRedDesc * 8)]
+
+
+class TrainSDesc(ctypes.Structure):
+    """kdlae_debug_train_s_desc (include/kdlae.h): the C field `in` is `inp` here."""
+
+    _fields_ = [("op", c_int), ("inp", c_void_p * 3), ("ldi", c_int * 3), ("bias", c_void_p),
+                ("out", c_void_p), ("ldo", c_int),
+                ("C", c_int), ("O", c_int), ("B", c_int), ("F", c_int), ("H", c_int), ("W", c_int),
+                ("accumulate", c_int), ("dir", c_int)]
 
 
 _lib = None
@@ -214,8 +242,10 @@ def lib() -> ctypes.CDLL:
     L.kdlae_metric_psnr.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                     c_int, c_int, c_void_p, c_void_p, c_void_p]
     L.kdlae_debug_tgemm.argtypes = [c_void_p, c_void_p]
-    for f in ("kdlae_debug_gemm", "kdlae_debug_gram", "kdlae_debug_ln", "kdlae_debug_small_in"):
+    for f in ("kdlae_debug_gemm", "kdlae_debug_gram", "kdlae_debug_ln", "kdlae_debug_small_in",
+              "kdlae_debug_train", "kdlae_debug_train_s"):
         getattr(L, f).argtypes = [c_void_p, c_void_p]
+    L.kdlae_debug_train_blocks.argtypes = [c_int, c_int64, c_int, c_int, c_int64]
     L.kdlae_debug_gemm_variant.argtypes = [c_int, c_int, ctypes.POINTER(c_int)]
     for name in EXPORTS:
         if not name.endswith(("_last_error", "_abi_version", "_workspace_bytes", "_padded_size", "_num_floats",

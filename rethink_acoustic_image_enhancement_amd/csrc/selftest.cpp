@@ -2,15 +2,28 @@
 // of internal kernel families on caller buffers, so tests/test_kernel_variants_gpu.py can reach every
 // compiled variant against a torch reference.  Not part of the drop-in boundary; nothing here is on
 // a forward / training path.
+//   kdlae_debug_tgemm                      the training GEMM family (rows / cols / tiled kernels)
+//   kdlae_debug_gemm, _gemm_variant        the inference implicit-GEMM family
+//   kdlae_debug_gram                       MDTA dwconv + Gram
+//   kdlae_debug_ln                         training LayerNorm forward / backward
+//   kdlae_debug_small_in                   small-input 3x3 / 3x3x3 conv
+//   kdlae_debug_bn                         ASDQE training BatchNorm / upsample kernels
+//   kdlae_debug_train, _train_blocks       the KDLAE-T step's non-GEMM kernels: MDTA softmax core and its
+//                                          backward, depthwise / gate family, small-side 3x3 weight gradient,
+//                                          column reductions, layout kernels (tests/test_train_kernels_gpu.py)
+//   kdlae_debug_train_s                    the KDLAE-S step's im2col / col2im, weight permute, ReLU mask,
+//                                          max-pool backward, transposed-conv scatter
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdint>
 #include <string>
 
 #include "../../include/kdlae.h"
 #include "runtime.h"
 #include "train_a.h"
 #include "train_kernels.h"
+#include "train_s.h"
 
 namespace tr = kdlae::train;
 using kdlae::fail;
@@ -264,5 +277,240 @@ extern "C" int kdlae_debug_bn(const kdlae_debug_bn_desc* d, void* stream) {
     default: return fail(KDLAE_EINVAL_CONFIG, "op must be 0..5");
   }
   if (e != hipSuccess) return fail(KDLAE_EHIP, std::string("kdlae_debug_bn: ") + hipGetErrorString(e));
+  return KDLAE_OK;
+}
+
+// ---- non-GEMM training kernels (kdlae_debug_train / kdlae_debug_train_s): argument checks first,
+// so that a wrong test argument is an error code and never a device fault
+namespace {
+
+constexpr long long kMaxIdx = 1LL << 31;  // the kernels' 32-bit index math; far above any self-test shape
+inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// a [pixels][ld] view of `width` used columns
+inline bool view_ok(const void* p, int ld, int width, long long pixels) {
+  return p && width >= 1 && ld >= width && pixels >= 1 && pixels * ld < kMaxIdx;
+}
+
+}  // namespace
+
+extern "C" int kdlae_debug_train_blocks(int which, int64_t n, int a, int b, int64_t cap) {
+  if (which == 0) {
+    if (n < 1 || a < 1 || b < 1 || n * a * b >= kMaxIdx) return -1;
+    return tr::dwg_blocks((int)n, a, b);
+  }
+  if (which == 1) {
+    if (n < 1 || n >= kMaxIdx || !tr::dw3_small_ok(a, b) || cap < (int64_t)a * b * 9) return -1;
+    return tr::dw3_small_blocks(n, a, b, (size_t)cap);
+  }
+  return -1;
+}
+
+extern "C" int kdlae_debug_train(const kdlae_debug_train_desc* d, void* stream) {
+  if (!d) return fail(KDLAE_EINVAL_CONFIG, "null descriptor");
+  hipStream_t s = (hipStream_t)stream;
+  const int C = d->C;
+  const bool geo = d->Bn >= 1 && d->H >= 1 && d->W >= 1 && (long long)d->Bn * d->H * d->W < kMaxIdx;
+  const long long px = geo ? (long long)d->Bn * d->H * d->W : 0;
+  auto in_ok = [&](int i, int width, long long pixels) { return view_ok(d->in[i], d->ldi[i], width, pixels); };
+  auto out_ok = [&](int i, int width, long long pixels) { return view_ok(d->out[i], d->ldo[i], width, pixels); };
+  // the buffer-descriptor kernels address one image with 32-bit byte offsets below their sentinel
+  auto img_ok = [&](int ld) { return (long long)d->H * d->W * ld * 4 < (1LL << 30); };
+  const char* bad = "bad geometry";
+  hipError_t e = hipSuccess;
+  switch (d->op) {
+    case 0:
+    case 1: {
+      if (d->heads < 1 || C < 1 || C % d->heads || C / d->heads > 128 || d->Bn < 1 || d->Bn > 65535 / d->heads)
+        return fail(KDLAE_EINVAL_SHAPE, "attention: C = heads * Ch with Ch <= 128");
+      const int Ch = C / d->heads;
+      if (!d->in[0] || !d->in[1] || !d->w || !d->out[0]) return fail(KDLAE_EINVAL_CONFIG, "null operand");
+      if (d->op == 0) {
+        e = tr::launch_attn_softmax(d->in[0], d->in[1], d->w, d->Bn, C, d->heads, d->out[0], s);
+        break;
+      }
+      if (!d->in[2] || !d->in[3] || !d->out[1] || !d->out[2] || !d->out[3])
+        return fail(KDLAE_EINVAL_CONFIG, "null operand");
+      if (((size_t)Ch * Ch + 4) * sizeof(float) > 65536)
+        return fail(KDLAE_EINVAL_SHAPE, "attention backward: the Ch x Ch tile must fit 64 KiB of LDS");
+      e = tr::launch_attn_bwd(d->in[0], d->in[1], d->w, d->in[2], d->in[3], d->Bn, C, d->heads, d->out[0], d->out[1],
+                              d->out[2], d->out[3], s);
+      break;
+    }
+    case 2: {
+      if (!geo || !d->w || !in_ok(0, C, px) || !out_ok(0, C, px)) return fail(KDLAE_EINVAL_SHAPE, bad);
+      // the tile kernel (both strides % 4 == 0) moves float4 quads
+      if (d->ldi[0] % 4 == 0 && d->ldo[0] % 4 == 0 && d->ldi[0] >= (C + 3) / 4 * 4 && (!al16(d->in[0]) || !al16(d->out[0])))
+        return fail(KDLAE_EINVAL_SHAPE, "dw_fwd: views with ld % 4 == 0 must be 16-byte aligned");
+      e = tr::launch_dw_fwd(d->in[0], d->ldi[0], d->w, d->bias, d->flag ? 1 : 0, C, d->Bn, d->H, d->W, d->out[0],
+                            d->ldo[0], s);
+      break;
+    }
+    case 3: {
+      if (!geo || !d->w || C > (1 << 20) || !in_ok(0, 2 * C, px) || !out_ok(0, C, px) || (d->out[1] && !out_ok(1, 2 * C, px)) ||
+          !img_ok(std::max(d->ldi[0], std::max(d->ldo[0], d->out[1] ? d->ldo[1] : 0))))
+        return fail(KDLAE_EINVAL_SHAPE, bad);
+      e = tr::launch_dwgate_fwd(d->in[0], d->ldi[0], d->w, d->bias, C, d->Bn, d->H, d->W, d->out[1],
+                                d->out[1] ? d->ldo[1] : 0,
+                                d->out[0], d->ldo[0], s);
+      break;
+    }
+    case 4:
+    case 5:
+    case 6: {
+      if (!geo || !d->w || C < 1 || C > (1 << 20)) return fail(KDLAE_EINVAL_SHAPE, bad);
+      const int Ct = d->op == 6 ? C : 2 * C;  // channels of y / dy (and of the partial rows)
+      const int nin = d->op == 4 ? 3 : 2;
+      // in0: dg (C) or dyd (Ct); the rest: yd / y (Ct)
+      int ldmax = d->ldo[0];
+      for (int i = 0; i < nin; ++i) {
+        if (!in_ok(i, (i == 0 && d->op != 6) ? C : Ct, px)) return fail(KDLAE_EINVAL_SHAPE, bad);
+        ldmax = std::max(ldmax, d->ldi[i]);
+      }
+      if (!out_ok(0, Ct, px) || !img_ok(ldmax)) return fail(KDLAE_EINVAL_SHAPE, bad);
+      if (!d->part || d->part_floats < (long long)tr::dwg_blocks(d->Bn, d->H, d->W) * 10 * Ct)
+        return fail(KDLAE_EINVAL_SHAPE, "part must hold blocks * 10 * channels floats");
+      if (d->op == 4)
+        e = tr::launch_dwgate_bwd(d->in[0], d->ldi[0], d->in[1], d->ldi[1], d->in[2], d->ldi[2], d->w, C, d->Bn, d->H,
+                                  d->W, d->out[0], d->ldo[0], d->part, s);
+      else if (d->op == 5)
+        e = tr::launch_dwgate_bwd_rc(d->in[0], d->ldi[0], d->in[1], d->ldi[1], d->w, d->bias, C, d->Bn, d->H, d->W,
+                                     d->out[0], d->ldo[0], d->part, s);
+      else
+        e = tr::launch_dw_bwd(d->in[0], d->ldi[0], d->in[1], d->ldi[1], d->w, C, d->Bn, d->H, d->W, d->out[0],
+                              d->ldo[0], d->part, s);
+      break;
+    }
+    case 7: {
+      if (!tr::dw3_small_ok(C, d->C2)) return fail(KDLAE_EINVAL_SHAPE, "dw3_small: Cout == 3 or Cin in {3, 4}, wide side <= 256");
+      if (!geo || !in_ok(0, d->C2, px) || !in_ok(1, C, px) || d->flag < 1 || d->flag > 64 || d->nblk < 1 || d->nblk > 65535)
+        return fail(KDLAE_EINVAL_SHAPE, bad);
+      if (!d->part || d->part_floats < (long long)d->nblk * C * d->C2 * 9)
+        return fail(KDLAE_EINVAL_SHAPE, "part must hold nblk * Cout * Cin * 9 floats");
+      e = tr::launch_dw3_small(d->in[0], d->ldi[0], d->in[1], d->ldi[1], C, d->C2, d->Bn, d->H, d->W, d->flag, d->part,
+                               d->nblk, s);
+      break;
+    }
+    case 8: {
+      if (d->nseg < 1 || d->nseg > 65535 || d->nblk < 1 || d->nblk > 65535 || d->P < 1 || d->P >= kMaxIdx ||
+          !in_ok(0, C, d->P * d->nseg))
+        return fail(KDLAE_EINVAL_SHAPE, bad);
+      if (!d->part || d->part_floats < (long long)d->nseg * d->nblk * C)
+        return fail(KDLAE_EINVAL_SHAPE, "part must hold nseg * nblk * ncols floats");
+      e = tr::launch_colsum(d->in[0], d->ldi[0], C, d->P, d->nseg, d->flag ? 1 : 0, d->part, d->nblk, s);
+      break;
+    }
+    case 9: {
+      if (!d->in[0] || !d->out[0]) return fail(KDLAE_EINVAL_CONFIG, "null operand");
+      if (d->nseg < 1 || d->nseg > 65535 || d->nblk < 1 || C < 1 || (d->pstride != 0 && d->pstride < C) ||
+          (long long)d->nseg * d->nblk * std::max(d->pstride, C) >= kMaxIdx)
+        return fail(KDLAE_EINVAL_SHAPE, bad);
+      e = tr::launch_part_reduce(d->in[0], d->nblk, C, d->nseg, d->out[0], d->accumulate ? 1 : 0, d->scale, s,
+                                 d->pstride);
+      break;
+    }
+    case 10: {
+      if (d->nred < 1 || d->nred > tr::kRedBatch) return fail(KDLAE_EINVAL_SHAPE, "nred must be 1..8");
+      tr::RedDesc r[tr::kRedBatch];
+      for (int j = 0; j < d->nred; ++j) {
+        const kdlae_debug_train_red& q = d->red[j];
+        if (!q.part || !q.out) return fail(KDLAE_EINVAL_CONFIG, "null operand");
+        if (q.nblk < 1 || q.ncols < 1 || q.pstride < q.ncols || (long long)q.nblk * q.pstride >= kMaxIdx)
+          return fail(KDLAE_EINVAL_SHAPE, bad);
+        r[j].part = q.part; r[j].out = q.out; r[j].nblk = q.nblk; r[j].ncols = q.ncols; r[j].pstride = q.pstride;
+        r[j].scale = q.scale;
+      }
+      e = tr::launch_part_reduce_multi(r, d->nred, s);
+      break;
+    }
+    case 11: {
+      if (!geo || C < 1 || C > (1 << 20) || (d->flag != 0 && d->flag != 1)) return fail(KDLAE_EINVAL_SHAPE, bad);
+      const bool un = d->flag == 0;  // H, W: the low-resolution grid
+      if (!in_ok(0, un ? C : 4 * C, un ? 4 * px : px) || !out_ok(0, un ? 4 * C : C, un ? px : 4 * px))
+        return fail(KDLAE_EINVAL_SHAPE, bad);
+      e = tr::launch_shuffle(d->in[0], d->ldi[0], d->out[0], d->ldo[0], C, d->Bn, d->H, d->W, d->flag, s);
+      break;
+    }
+    case 12: {
+      if (d->P < 1 || d->P >= kMaxIdx || d->zero_to < 0 || !in_ok(0, C, d->P) || !out_ok(0, std::max(C, d->zero_to), d->P))
+        return fail(KDLAE_EINVAL_SHAPE, bad);
+      e = tr::launch_copy_cols(d->in[0], d->ldi[0], d->out[0], d->ldo[0], C, d->P, d->accumulate ? 1 : 0, s, d->zero_to);
+      break;
+    }
+    case 13:
+    case 14: {
+      if (d->Bn < 1 || d->P < 1 || C < 1 || (long long)d->Bn * d->P >= kMaxIdx || !d->in[0] || !d->out[0])
+        return fail(KDLAE_EINVAL_SHAPE, bad);
+      const long long pixels = (long long)d->Bn * d->P;
+      if (pixels * C >= kMaxIdx) return fail(KDLAE_EINVAL_SHAPE, bad);
+      if (d->op == 13) {
+        if (!out_ok(0, C, pixels)) return fail(KDLAE_EINVAL_SHAPE, bad);
+        e = tr::launch_nchw_to_nhwc(d->in[0], C, d->Bn, d->P, d->out[0], d->ldo[0], d->accumulate ? 1 : 0, s);
+      } else {
+        if (!in_ok(0, C, pixels)) return fail(KDLAE_EINVAL_SHAPE, bad);
+        e = tr::launch_nhwc_to_nchw(d->in[0], d->ldi[0], d->in[1], C, d->Bn, d->P, d->out[0], s);
+      }
+      break;
+    }
+    case 15: {
+      if (!d->w || !d->out[0]) return fail(KDLAE_EINVAL_CONFIG, "null operand");
+      if ((d->flag != 2 && d->flag != 3) || C < 1 || d->C2 < 1 || 9LL * C * d->C2 >= kMaxIdx)
+        return fail(KDLAE_EINVAL_SHAPE, "pack_w3: mode 2 or 3, Cg, N >= 1");
+      e = tr::launch_pack_w3(d->w, C, d->C2, d->flag, d->out[0], s);
+      break;
+    }
+    default: return fail(KDLAE_EINVAL_CONFIG, "op must be 0..15");
+  }
+  if (e != hipSuccess) return fail(KDLAE_EHIP, std::string("kdlae_debug_train: ") + hipGetErrorString(e));
+  return KDLAE_OK;
+}
+
+extern "C" int kdlae_debug_train_s(const kdlae_debug_train_s_desc* d, void* stream) {
+  if (!d) return fail(KDLAE_EINVAL_CONFIG, "null descriptor");
+  hipStream_t s = (hipStream_t)stream;
+  const int C = d->C;
+  const char* bad = "bad geometry";
+  if (d->op == 2) {
+    if (!d->in[0] || !d->out) return fail(KDLAE_EINVAL_CONFIG, "null operand");
+    if (d->O < 1 || C < 1 || 27LL * d->O * C >= kMaxIdx || (d->dir != 0 && d->dir != 1)) return fail(KDLAE_EINVAL_SHAPE, bad);
+    const hipError_t e = tr::launch_wperm(d->in[0], d->out, d->O, C, d->dir, s);
+    if (e != hipSuccess) return fail(KDLAE_EHIP, std::string("kdlae_debug_train_s: ") + hipGetErrorString(e));
+    return KDLAE_OK;
+  }
+  if (d->B < 1 || d->F < 1 || d->H < 1 || d->W < 1 || C < 1 || C > (1 << 16) ||
+      (long long)d->B * d->F * d->H * d->W * 27 * C >= kMaxIdx)
+    return fail(KDLAE_EINVAL_SHAPE, bad);
+  const long long px = (long long)d->B * d->F * d->H * d->W;
+  auto in_ok = [&](int i, int width, long long pixels) { return view_ok(d->in[i], d->ldi[i], width, pixels); };
+  hipError_t e = hipSuccess;
+  switch (d->op) {
+    case 0:
+      if (!in_ok(0, C, px) || !d->out) return fail(KDLAE_EINVAL_SHAPE, bad);
+      e = tr::launch_im2col3d(d->in[0], d->ldi[0], C, d->B, d->F, d->H, d->W, d->out, s);
+      break;
+    case 1:
+      if (!d->in[0] || !view_ok(d->out, d->ldo, C, px)) return fail(KDLAE_EINVAL_SHAPE, bad);
+      if (C % 4 || d->ldo % 4 || !al16(d->out) || !al16(d->in[0]))
+        return fail(KDLAE_EINVAL_SHAPE, "col2im3d: C % 4 == 0, ld % 4 == 0 and 16-byte aligned operands");
+      e = tr::launch_col2im3d(d->in[0], C, d->B, d->F, d->H, d->W, d->out, d->ldo, d->accumulate ? 1 : 0, s);
+      break;
+    case 3:
+      if (!in_ok(0, C, px) || !view_ok(d->out, d->ldo, C, px)) return fail(KDLAE_EINVAL_SHAPE, bad);
+      e = tr::launch_relu_mask(d->out, d->ldo, d->in[0], d->ldi[0], C, px, s);
+      break;
+    case 4:  // H, W: the pooled grid
+      if (!in_ok(0, C, 4 * px) || !in_ok(1, C, px) || (d->in[2] && !in_ok(2, C, 4 * px)) || !view_ok(d->out, d->ldo, C, 4 * px))
+        return fail(KDLAE_EINVAL_SHAPE, bad);
+      e = tr::launch_maxpool2_bwd(d->in[0], d->ldi[0], d->in[1], d->ldi[1], d->in[2], d->ldi[2], d->out, d->ldo, C, d->B,
+                                  d->F, d->H, d->W, s);
+      break;
+    case 5:  // H, W: the output grid
+      if (d->H % 2 || d->W % 2 || !in_ok(0, 4 * C, px / 4) || !in_ok(1, C, px) || !view_ok(d->out, d->ldo, C, px))
+        return fail(KDLAE_EINVAL_SHAPE, bad);
+      e = tr::launch_upshuffle_add(d->in[0], d->ldi[0], d->bias, d->in[1], d->ldi[1], d->out, d->ldo, C, d->B, d->F, d->H,
+                                   d->W, s);
+      break;
+    default: return fail(KDLAE_EINVAL_CONFIG, "op must be 0..5");
+  }
+  if (e != hipSuccess) return fail(KDLAE_EHIP, std::string("kdlae_debug_train_s: ") + hipGetErrorString(e));
   return KDLAE_OK;
 }

@@ -181,3 +181,78 @@ def test_asdqe_param_enumeration(kw):
 def test_asdqe_config_validation():
     assert _a_create(DenoiseRatePredictor(dim=8))[0] == 2
     assert _a_create(DenoiseRatePredictor(in_channels=5))[0] == 2
+
+
+# ------------------------------------------------------------------ training-kernel self-test entries
+def test_debug_train_entries_refuse_bad_arguments():
+    """kdlae_debug_train / kdlae_debug_train_s validate before they launch: a wrong test argument is an
+    error code (1 = EINVAL_SHAPE, 2 = EINVAL_CONFIG), never a device fault.  The pointers here are never
+    dereferenced."""
+    from rethink_acoustic_image_enhancement_amd._lib import TrainDesc, TrainSDesc
+
+    L = _lib.lib()
+    P = 0x1000  # a non-null, 16-byte aligned "device pointer"
+
+    def t(ins=(), outs=(), **kw):
+        d = TrainDesc()
+        for i, (p, ld) in enumerate(ins):
+            d.inp[i], d.ldi[i] = p, ld
+        for i, (p, ld) in enumerate(outs):
+            d.out[i], d.ldo[i] = p, ld
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return L.kdlae_debug_train(ctypes.byref(d), None)
+
+    def s(ins=(), **kw):
+        d = TrainSDesc()
+        for i, (p, ld) in enumerate(ins):
+            d.inp[i], d.ldi[i] = p, ld
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return L.kdlae_debug_train_s(ctypes.byref(d), None)
+
+    geo = dict(Bn=2, H=8, W=8)
+    assert L.kdlae_debug_train(None, None) == 2 and L.kdlae_debug_train_s(None, None) == 2
+    assert t(op=99) == 2 and s(op=99, B=1, F=1, H=2, W=2, C=4) == 2
+    # attention: Ch > 128, C not a multiple of heads, null operand
+    assert t(op=0, ins=[(P, 0), (P, 0)], outs=[(P, 0)], w=P, C=258, heads=2, Bn=1) == 1
+    assert t(op=0, ins=[(P, 0), (P, 0)], outs=[(P, 0)], w=P, C=9, heads=2, Bn=1) == 1
+    assert t(op=0, ins=[(P, 0), (None, 0)], outs=[(P, 0)], w=P, C=16, heads=2, Bn=1) == 2
+    assert t(op=1, ins=[(P, 0)] * 4, outs=[(P, 0)] * 3, w=P, C=16, heads=2, Bn=1) == 2
+    # the backward's Ch x Ch LDS tile: Ch = 128 is past 64 KiB
+    assert t(op=1, ins=[(P, 0)] * 4, outs=[(P, 0)] * 4, w=P, C=256, heads=2, Bn=1) == 1 and "LDS" in _lib.last_error()
+    # ld < C, null weight, misaligned float4 view
+    assert t(op=2, ins=[(P, 7)], outs=[(P, 8)], w=P, C=8, **geo) == 1
+    assert t(op=2, ins=[(P, 8)], outs=[(P, 8)], w=None, C=8, **geo) == 1
+    assert t(op=2, ins=[(P + 4, 8)], outs=[(P, 8)], w=P, C=8, **geo) == 1
+    # gate family: y narrower than 2 hid; partial capacity
+    assert t(op=3, ins=[(P, 9)], outs=[(P, 5)], w=P, C=5, **geo) == 1
+    nblk = L.kdlae_debug_train_blocks(0, 2, 8, 8, 0)
+    assert nblk == 2 * 1 * 2  # 16 columns x 4 rows per block
+    ok = dict(ins=[(P, 5), (P, 10), (P, 10)], outs=[(P, 10)], w=P, C=5, part=P)
+    assert t(op=4, part_floats=nblk * 100 - 1, **ok, **geo) == 1
+    assert t(op=6, ins=[(P, 5), (P, 5)], outs=[(P, 5)], w=P, C=5, part=None, part_floats=1 << 20, **geo) == 1
+    assert "part" in _lib.last_error()
+    # dw3_small: the instance rule, capacity
+    assert t(op=7, ins=[(P, 5), (P, 5)], C=5, C2=5, flag=1, nblk=1, part=P, part_floats=1 << 20, **geo) == 1
+    assert "dw3_small" in _lib.last_error()
+    assert t(op=7, ins=[(P, 3), (P, 5)], C=5, C2=3, flag=1, nblk=4, part=P, part_floats=4 * 135 - 1, **geo) == 1
+    assert L.kdlae_debug_train_blocks(1, 128, 5, 5, 1 << 20) == -1 and L.kdlae_debug_train_blocks(2, 1, 1, 1, 0) == -1
+    assert L.kdlae_debug_train_blocks(1, 198, 10, 3, 64 * 270) == 5
+    # reductions
+    assert t(op=8, ins=[(P, 4)], C=4, P=10, nseg=1, nblk=2, part=P, part_floats=7) == 1
+    assert t(op=9, ins=[(P, 0)], outs=[(P, 0)], C=4, nblk=2, nseg=1, pstride=3) == 1
+    assert t(op=10, nred=9) == 1 and t(op=10, nred=1) == 2
+    # layout
+    assert t(op=11, ins=[(P, 3)], outs=[(P, 11)], C=3, flag=0, **geo) == 1
+    assert t(op=12, ins=[(P, 5)], outs=[(P, 7)], C=5, P=4, zero_to=8) == 1
+    assert t(op=15, outs=[(P, 0)], w=P, C=4, C2=4, flag=1) == 1
+    # KDLAE-S
+    sg = dict(B=1, F=1, H=4, W=4)
+    assert s(op=0, ins=[(P, 3)], out=P, C=4, **sg) == 1
+    assert s(op=1, ins=[(P, 0)], out=P, ldo=6, C=6, **sg) == 1           # C % 4 != 0
+    assert s(op=1, ins=[(P, 0)], out=P + 4, ldo=8, C=8, **sg) == 1       # misaligned
+    assert s(op=2, ins=[(P, 0)], out=P, O=4, C=4, dir=2) == 1
+    assert s(op=4, ins=[(P, 4), (P, 3)], out=P, ldo=4, C=4, **sg) == 1
+    assert s(op=5, ins=[(P, 16), (P, 4)], out=P, ldo=4, C=4, B=1, F=1, H=3, W=4) == 1
+    assert s(op=5, ins=[(P, 15), (P, 4)], out=P, ldo=4, C=4, **sg) == 1  # U narrower than 4 C
