@@ -418,7 +418,7 @@ int kdlae_metric_psnr(const float* pred, const float* gt, int B, int C, int Hs, 
  * or training path).  tests/test_kernel_variants*_gpu.py: kdlae_debug_tgemm, kdlae_debug_gemm,
  * kdlae_debug_gram, kdlae_debug_ln, kdlae_debug_small_in, kdlae_debug_bn;
  * tests/test_train_kernels_gpu.py: kdlae_debug_train, kdlae_debug_train_s (the training steps'
- * non-GEMM kernels).
+ * non-GEMM kernels); tests/test_infer_kernels_gpu.py: kdlae_debug_infer (the forward paths' other kernels).
  * One launch of the training GEMM family on caller device buffers:
  *   C(m, n) = sum_k A(m, k) B(k, n) [+ bias[n]] [+ rs[n] R(m, n)], batch z = z1 * nz2 + z2, every
  *   operand offset by z1 * b?1 + z2 * b?2 (floats); amode 1 = implicit 3x3 im2col of the NHWC view A
@@ -613,6 +613,57 @@ typedef struct kdlae_debug_train_s_desc {
   int accumulate, dir;
 } kdlae_debug_train_s_desc;
 int kdlae_debug_train_s(const kdlae_debug_train_s_desc* d, void* stream);
+
+/* The forward paths' kernels outside the GEMM / Gram families, one launch sequence per call on caller
+ * buffers (tests/test_infer_kernels_gpu.py; launch interface and operand meaning: csrc/kernels.h).
+ * NHWC views of Bn x F x H x W pixels (F = 0 means 1) at the pixel stride given beside each pointer.
+ * Every launcher precondition (null operand, ld < width, a misaligned float4 view, an unsupported
+ * channel count, scratch too small, ...) returns KDLAE_EINVAL_* before any launch.  Weights that a
+ * kernel reads as split records (mfma3.h) are handed in f32 fragment order [ntiles][kgroups][64][4]
+ * (element (l, e) of (t, g) = W(16 t + l % 16, 16 g + 4 (l / 16) + e)) and converted into scratch the
+ * call owns.  dw blocks: per 16-channel chunk g 512 floats, weight of tap t, half h (0 = x1, 1 = x2),
+ * channel c at 32 t + 16 h + c, bias at 288 + 16 h + c (gdfn.hip).
+ *   op 0 gdfn_out       in0 = project_in rows [P][2 hidS] chunk-interleaved (ldi0 == 2 hidS), w0 = dw blocks,
+ *                       w1 = project_out [C/16][hidS/16] fragments, bias0 [C] (or null), R / ldr (or null; may be
+ *                       out0), zeros (>= 16 zero floats) -> out0 (C)
+ *   op 1 ffn_fused      in0 = x (C), ln, w0 = project_in [2 hidS/16][C/16] fragments (chunk-interleaved rows),
+ *                       bias0 [2 hidS] (chunk-interleaved, or null), w1 = dw blocks, w2 = project_out fragments,
+ *                       bias1 [C] (or null) -> out0 = x + ffn(LN(x)) (must not overlap in0)
+ *   op 2 mdta_fused     in0 = x (C), ln, w0 = qkv [3C/16][C/16] fragments, bias0 [3C] (or null), w1 = wdw [9][3C],
+ *                       bias1 = bdw [3C] (or null), nseg, seg_rows, scratch = the Gram slots (Bn * (W/16) * nseg *
+ *                       (C^2 + 2C) floats) -> out0 = v (C), out1 = reduced [Bn][C^2 + 2C] (layout: kdlae_debug_gram)
+ *   op 3 attn_fold      in0 = reduced [Bn heads][Ch^2 + 2 Ch], w0 = project_out weight [C][C], w1 = temperature [heads]
+ *                       -> out0 = M per image as split records [C/16][ceil(C/32)][3][64] x 16 B
+ *   op 4 dwconv_gate    in0 = x (x1 at [0, hidS), x2 at [hidS, 2 hidS)), w0 [9][2 hidS], bias0 [2 hidS] (or null)
+ *                       -> out0 (hidS); hidS % 4 == 0
+ *   op 5 conv_lds       in0 (cin_pad), w0 = [ntiles][9 kt cin_pad/16] fragments (k = tap cin_pad + c), bias0
+ *                       [16 ntiles] (or null), kt, relu, out_mode 0 / 1 (PixelUnshuffle) / 2 (PixelShuffle), nout;
+ *                       use_wp3: also hand the kernel split records (kt 1: of w0; kt 3: of w1, the same weights
+ *                       in k-group order c * 28 + tap, tap 27 zero) -> out0
+ *   op 6 conv_small_out in0 (C = Cin, a multiple of 16), C2 = Cout <= 4, ks, w0 [Cout][Cin][ks][ks] (wt: the
+ *                       transposed conv's [Cin][Cout][3][3]), bias0 (or null); out_nchw: out0 [Bn][Cout][F H W],
+ *                       in1 = res of that shape (or null); else out0 NHWC (ldo0), R / ldr = NHWC residual (may be
+ *                       out0), in2 = extra [Bn][F H W] copied into channel Cout (or null)
+ *   op 7 conv3d_c16     in0 (16), w0 = [9 kt][64][4] fragments, bias0 [16], kt 1 / 3, relu -> out0 (16)
+ *   op 8 maxpool2       in0 [Bn frames][H][W] (C) -> out0 [Bn][H/2][W/2] (C); C % 4 == 0
+ *   op 9 gap + head     in0 [Bn][H W] (C), slots, scratch (Bn slots C floats), w0 [M][C], bias0 [M], w1 [N1][M],
+ *                       bias1, w2 [N2][N1], bias2, w3 [N2], bias3 [1] -> out0 = score [Bn] */
+typedef struct kdlae_debug_infer_desc {
+  int op;
+  const float* in[3]; int ldi[3];
+  const float* w[4];
+  const float* bias[4];
+  const float* R; int ldr;
+  float* out[2]; int ldo[2];
+  float* scratch; int64_t scratch_floats;
+  const float* zeros;
+  int C, C2, heads, Bn, F, H, W;
+  int hidS, ln, nseg, seg_rows;
+  int ntiles, cin_pad, kt, ks, relu, out_mode, nout, use_wp3;
+  int out_nchw, wt, slots;
+  int M, N1, N2;
+} kdlae_debug_infer_desc;
+int kdlae_debug_infer(const kdlae_debug_infer_desc* d, void* stream);
 
 #ifdef __cplusplus
 }

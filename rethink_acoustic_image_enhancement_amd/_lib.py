@@ -53,6 +53,7 @@ EXPORTS = (
     "kdlae_debug_bn",
     "kdlae_metric_scratch_bytes", "kdlae_metric_psnr",
     "kdlae_debug_train", "kdlae_debug_train_blocks", "kdlae_debug_train_s",
+    "kdlae_debug_infer",
 )
 
 
@@ -107,6 +108,21 @@ class TrainSDesc(ctypes.Structure):
                 ("out", c_void_p), ("ldo", c_int),
                 ("C", c_int), ("O", c_int), ("B", c_int), ("F", c_int), ("H", c_int), ("W", c_int),
                 ("accumulate", c_int), ("dir", c_int)]
+
+
+class InferDesc(ctypes.Structure):
+    """kdlae_debug_infer_desc (include/kdlae.h): the C field `in` is `inp` here."""
+
+    _fields_ = [("op", c_int), ("inp", c_void_p * 3), ("ldi", c_int * 3), ("w", c_void_p * 4),
+                ("bias", c_void_p * 4), ("R", c_void_p), ("ldr", c_int),
+                ("out", c_void_p * 2), ("ldo", c_int * 2), ("scratch", c_void_p), ("scratch_floats", c_int64),
+                ("zeros", c_void_p),
+                ("C", c_int), ("C2", c_int), ("heads", c_int), ("Bn", c_int), ("F", c_int), ("H", c_int), ("W", c_int),
+                ("hidS", c_int), ("ln", c_int), ("nseg", c_int), ("seg_rows", c_int),
+                ("ntiles", c_int), ("cin_pad", c_int), ("kt", c_int), ("ks", c_int), ("relu", c_int),
+                ("out_mode", c_int), ("nout", c_int), ("use_wp3", c_int),
+                ("out_nchw", c_int), ("wt", c_int), ("slots", c_int),
+                ("M", c_int), ("N1", c_int), ("N2", c_int)]
 
 
 _lib = None
@@ -243,7 +259,7 @@ def lib() -> ctypes.CDLL:
                                     c_int, c_int, c_void_p, c_void_p, c_void_p]
     L.kdlae_debug_tgemm.argtypes = [c_void_p, c_void_p]
     for f in ("kdlae_debug_gemm", "kdlae_debug_gram", "kdlae_debug_ln", "kdlae_debug_small_in",
-              "kdlae_debug_train", "kdlae_debug_train_s"):
+              "kdlae_debug_train", "kdlae_debug_train_s", "kdlae_debug_infer"):
         getattr(L, f).argtypes = [c_void_p, c_void_p]
     L.kdlae_debug_train_blocks.argtypes = [c_int, c_int64, c_int, c_int, c_int64]
     L.kdlae_debug_gemm_variant.argtypes = [c_int, c_int, ctypes.POINTER(c_int)]

@@ -13,6 +13,10 @@
 //                                          column reductions, layout kernels (tests/test_train_kernels_gpu.py)
 //   kdlae_debug_train_s                    the KDLAE-S step's im2col / col2im, weight permute, ReLU mask,
 //                                          max-pool backward, transposed-conv scatter
+//   kdlae_debug_infer                      the forward paths' kernels outside those families: fused GDFN tail,
+//                                          fused feed-forward half, fused MDTA pass 1, softmax + fold, dwconv
+//                                          gate, LDS-tiled convs, small-output conv, max-pool, ASDQE pool + head
+//                                          (tests/test_infer_kernels_gpu.py)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -512,5 +516,228 @@ extern "C" int kdlae_debug_train_s(const kdlae_debug_train_s_desc* d, void* stre
     default: return fail(KDLAE_EINVAL_CONFIG, "op must be 0..5");
   }
   if (e != hipSuccess) return fail(KDLAE_EHIP, std::string("kdlae_debug_train_s: ") + hipGetErrorString(e));
+  return KDLAE_OK;
+}
+
+// ---- inference kernels outside the GEMM / Gram families (kdlae_debug_infer): every launcher
+// precondition is checked here, so a wrong test argument is an error code and never a device fault
+namespace {
+
+// the per-image buffer-descriptor kernels (gdfn, ffn, mdta_fused) address one image with 32-bit byte offsets
+inline bool img_bytes_ok(int H, int W, int ld) { return (long long)H * W * ld * 4 < (1LL << 31); }
+
+// device scratch owned by one self-test call: released after the stream has drained
+struct SplitScratch {
+  float* p[3] = {nullptr, nullptr, nullptr};
+  hipStream_t s;
+  explicit SplitScratch(hipStream_t st) : s(st) {}
+  ~SplitScratch() {
+    (void)hipStreamSynchronize(s);
+    for (float* q : p)
+      if (q) (void)hipFree(q);
+  }
+  // split records of the f32 fragment block src [ntiles][kgroups][64][4]
+  hipError_t split(int i, const float* src, int ntiles, int kgroups) {
+    const long long n = kdlae::split3_floats(ntiles, kgroups);
+    hipError_t e = hipMalloc(&p[i], (size_t)n * sizeof(float));
+    if (e != hipSuccess) return e;
+    return kdlae::launch_split3(src, p[i], ntiles, kgroups, 1, 0, n, s);
+  }
+};
+
+}  // namespace
+
+extern "C" int kdlae_debug_infer(const kdlae_debug_infer_desc* d, void* stream) {
+  if (!d) return fail(KDLAE_EINVAL_CONFIG, "null descriptor");
+  hipStream_t s = (hipStream_t)stream;
+  const int C = d->C;
+  const int F = d->F > 0 ? d->F : 1;
+  const bool geo = d->Bn >= 1 && d->H >= 1 && d->W >= 1 && d->F >= 0 && (long long)d->Bn * F * d->H * d->W < kMaxIdx;
+  const long long px = geo ? (long long)d->Bn * F * d->H * d->W : 0;
+  auto in_ok = [&](int i, int width, long long pixels) { return view_ok(d->in[i], d->ldi[i], width, pixels); };
+  auto out_ok = [&](int i, int width, long long pixels) { return view_ok(d->out[i], d->ldo[i], width, pixels); };
+  // float4 access: 16-byte aligned base, pixel stride a multiple of 4
+  auto in4 = [&](int i) { return al16(d->in[i]) && d->ldi[i] % 4 == 0; };
+  auto out4 = [&](int i) { return al16(d->out[i]) && d->ldo[i] % 4 == 0; };
+  const char* bad = "bad geometry";
+  const char* null_op = "null operand";
+  const char* align = "float4 views: 16-byte aligned, ld % 4 == 0";
+  SplitScratch sc(s);
+  hipError_t e = hipSuccess;
+  switch (d->op) {
+    case 0: {  // fused GDFN tail
+      if (!d->w[0] || !d->w[1] || !d->zeros) return fail(KDLAE_EINVAL_CONFIG, null_op);
+      if (!kdlae::gdfn_supported(C, d->hidS)) return fail(KDLAE_EINVAL_SHAPE, "gdfn: C in {48, 96, 192, 384}, hidS % 16 == 0, hidS <= 256 (C <= 96) / 1024");
+      if (!geo || F != 1 || d->ldi[0] != 2 * d->hidS || !in_ok(0, 2 * d->hidS, px) || !out_ok(0, C, px) ||
+          (d->R && (d->ldr < C || px * d->ldr >= kMaxIdx)) || !img_bytes_ok(d->H, d->W, d->ldi[0]))
+        return fail(KDLAE_EINVAL_SHAPE, "gdfn: x is [P][2 hidS] exactly, out / R at least C wide");
+      if (!in4(0) || !out4(0) || !al16(d->w[0]) || !al16(d->bias[0]) || (d->R && (!al16(d->R) || d->ldr % 4)))
+        return fail(KDLAE_EINVAL_SHAPE, align);
+      HIPCHK(sc.split(0, d->w[1], C / 16, d->hidS / 16));
+      kdlae::GdfnParams p{};
+      p.x = d->in[0]; p.ld = d->ldi[0]; p.hidS = d->hidS; p.dw = d->w[0]; p.Wp = sc.p[0]; p.bias = d->bias[0];
+      p.R = d->R; p.ldr = d->ldr; p.out = d->out[0]; p.ldo = d->ldo[0];
+      p.Bn = d->Bn; p.H = d->H; p.W = d->W; p.zeros = d->zeros;
+      e = kdlae::launch_gdfn_out(p, C, s);
+      break;
+    }
+    case 1: {  // fused feed-forward half
+      if (!d->w[0] || !d->w[1] || !d->w[2]) return fail(KDLAE_EINVAL_CONFIG, null_op);
+      if (d->ln != 1 && d->ln != 2) return fail(KDLAE_EINVAL_CONFIG, "ln must be 1 or 2");
+      if (!kdlae::ffn_fused_supported(C, d->hidS)) return fail(KDLAE_EINVAL_SHAPE, "ffn: C in {48, 96}, hidS / 16 even, 2 .. 8 (C = 48) / 16");
+      if (!geo || F != 1 || !in_ok(0, C, px) || !out_ok(0, C, px) ||
+          !img_bytes_ok(d->H, d->W, std::max(d->ldi[0], d->ldo[0])))
+        return fail(KDLAE_EINVAL_SHAPE, bad);
+      if (!in4(0) || !out4(0) || !al16(d->w[1]) || !al16(d->bias[0]) || !al16(d->bias[1])) return fail(KDLAE_EINVAL_SHAPE, align);
+      {  // neighbouring tiles read x as halo: out must not overlap it
+        const uintptr_t x0 = (uintptr_t)d->in[0], x1 = x0 + (size_t)px * d->ldi[0] * 4;
+        const uintptr_t o0 = (uintptr_t)d->out[0], o1 = o0 + (size_t)px * d->ldo[0] * 4;
+        if (x0 < o1 && o0 < x1) return fail(KDLAE_EINVAL_SHAPE, "ffn: out must not overlap x");
+      }
+      HIPCHK(sc.split(0, d->w[0], 2 * d->hidS / 16, C / 16));
+      HIPCHK(sc.split(1, d->w[2], C / 16, d->hidS / 16));
+      kdlae::FfnParams p{};
+      p.x = d->in[0]; p.ldx = d->ldi[0]; p.out = d->out[0]; p.ldo = d->ldo[0]; p.ln = d->ln; p.hidS = d->hidS;
+      p.Win = sc.p[0]; p.bias_in = d->bias[0]; p.dw = d->w[1]; p.Wout = sc.p[1]; p.bias_out = d->bias[1];
+      p.Bn = d->Bn; p.H = d->H; p.W = d->W;
+      e = kdlae::launch_ffn_fused(p, C, s);
+      break;
+    }
+    case 2: {  // fused MDTA pass 1 + slot reduction
+      if (!d->w[0] || !d->w[1] || !d->scratch || !d->out[1]) return fail(KDLAE_EINVAL_CONFIG, null_op);
+      if (d->ln != 1 && d->ln != 2) return fail(KDLAE_EINVAL_CONFIG, "ln must be 1 or 2");
+      if (!geo || F != 1 || !kdlae::mdta_fused_supported(C, 1, d->H, d->W, d->nseg, d->seg_rows) ||
+          (long long)d->seg_rows * (d->nseg - 1) >= d->H)
+        return fail(KDLAE_EINVAL_SHAPE, "mdta_fused: C in {48, 96}, W % 16 == 0, H % 8 == 0, seg_rows % 8 == 0, nseg segments that cover H, none empty");
+      if (!in_ok(0, C, px) || !out_ok(0, C, px) || !img_bytes_ok(d->H, d->W, std::max(d->ldi[0], d->ldo[0])))
+        return fail(KDLAE_EINVAL_SHAPE, bad);
+      if (!in4(0) || !out4(0) || !al16(d->w[1]) || !al16(d->bias[0]) || !al16(d->bias[1]) || !al16(d->scratch))
+        return fail(KDLAE_EINVAL_SHAPE, align);
+      const int CT = C / 16, nslots = (d->W / 16) * d->nseg, slot_floats = CT * CT * 256 + 2 * C;
+      if ((long long)d->Bn * nslots * slot_floats > d->scratch_floats)
+        return fail(KDLAE_EINVAL_SHAPE, "scratch must hold Bn * nslots * slot_floats floats");
+      HIPCHK(sc.split(0, d->w[0], 3 * C / 16, C / 16));
+      kdlae::MdtaFusedParams p{};
+      p.x = d->in[0]; p.ldx = d->ldi[0]; p.ln = d->ln; p.Wqkv = sc.p[0]; p.bias = d->bias[0];
+      p.wdw = d->w[1]; p.bdw = d->bias[1]; p.v_out = d->out[0]; p.ldv = d->ldo[0]; p.partial = d->scratch;
+      p.nslots = nslots; p.slot_floats = slot_floats; p.nseg = d->nseg; p.seg_rows = d->seg_rows;
+      p.Bn = d->Bn; p.H = d->H; p.W = d->W;
+      e = kdlae::launch_mdta_fused(p, C, s);
+      if (e == hipSuccess) e = kdlae::launch_gram_reduce(d->scratch, d->out[1], d->Bn, 1, nslots, slot_floats, s);
+      break;
+    }
+    case 3: {  // softmax + fold
+      if (!d->in[0] || !d->w[0] || !d->w[1] || !d->out[0]) return fail(KDLAE_EINVAL_CONFIG, null_op);
+      if (d->heads < 1 || C < 16 || C % 16 || C % d->heads || (C / d->heads) % 16 || C / d->heads > 128 || d->Bn < 1 ||
+          d->Bn > 65535 || d->heads > 65535)
+        return fail(KDLAE_EINVAL_SHAPE, "attn_fold: C = heads * Ch, Ch a multiple of 16, 16 .. 128");
+      const int Ch = C / d->heads, CT = Ch / 16;
+      e = kdlae::launch_attn_fold(d->in[0], CT * CT * 256 + 2 * Ch, d->w[0], d->w[1], d->out[0], d->Bn, C, d->heads, s);
+      break;
+    }
+    case 4: {  // GDFN dwconv + gate
+      if (!d->w[0]) return fail(KDLAE_EINVAL_CONFIG, null_op);
+      if (!geo || F != 1 || d->hidS < 4 || d->hidS % 4 || d->hidS > (1 << 16) || !in_ok(0, 2 * d->hidS, px) ||
+          !out_ok(0, d->hidS, px))
+        return fail(KDLAE_EINVAL_SHAPE, "dwconv_gate: hidS % 4 == 0, x at least 2 hidS wide, out at least hidS");
+      if (!in4(0) || !out4(0) || !al16(d->w[0]) || !al16(d->bias[0])) return fail(KDLAE_EINVAL_SHAPE, align);
+      kdlae::GateParams p{};
+      p.x = d->in[0]; p.ld = d->ldi[0]; p.hidS = d->hidS; p.w = d->w[0]; p.b = d->bias[0];
+      p.out = d->out[0]; p.ldo = d->ldo[0]; p.Bn = d->Bn; p.H = d->H; p.W = d->W;
+      e = kdlae::launch_dwconv_gate(p, s);
+      break;
+    }
+    case 5: {  // LDS-tiled implicit-GEMM conv
+      if (!d->w[0] || (d->use_wp3 && d->kt == 3 && !d->w[1])) return fail(KDLAE_EINVAL_CONFIG, null_op);
+      if (!kdlae::conv_lds_supported(d->kt, d->ntiles, d->cin_pad) || d->cin_pad > 1024)
+        return fail(KDLAE_EINVAL_SHAPE, "conv_lds: kt 1 or 3, 2 .. 16 output tiles, cin_pad % 16 == 0");
+      if (!geo || (d->kt == 1 && F != 1) || d->out_mode < 0 || d->out_mode > 2 || !in_ok(0, d->cin_pad, px))
+        return fail(KDLAE_EINVAL_SHAPE, bad);
+      const int N = 16 * d->ntiles;
+      bool ok;
+      if (d->out_mode == 0) ok = out_ok(0, N, px);
+      else if (d->out_mode == 1)
+        ok = d->kt == 1 && d->H % 2 == 0 && d->W % 2 == 0 && d->nout >= 1 && d->nout <= N && out_ok(0, 4 * d->nout, px / 4);
+      else
+        ok = d->kt == 1 && d->nout >= 4 && d->nout % 4 == 0 && d->nout <= N && out_ok(0, d->nout / 4, 4 * px);
+      if (!ok) return fail(KDLAE_EINVAL_SHAPE, "conv_lds: store geometry (mode 1: even H, W, ldo >= 4 nout; mode 2: nout % 4 == 0, ldo >= nout / 4)");
+      if (!in4(0) || !out4(0) || !al16(d->w[0]) || !al16(d->bias[0])) return fail(KDLAE_EINVAL_SHAPE, align);
+      const int kgroups = 9 * d->kt * (d->cin_pad / 16);
+      if (d->use_wp3) {
+        // kt 1: split records of w0 itself; kt 3: of the tap-pair block w1 (k-group order c * 28 + tap, kdlae_s.cpp)
+        if (d->kt == 1) HIPCHK(sc.split(0, d->w[0], d->ntiles, kgroups));
+        else HIPCHK(sc.split(0, d->w[1], d->ntiles, 28 * (d->cin_pad / 16)));
+      }
+      kdlae::ConvLdsParams p{};
+      p.in = d->in[0]; p.ldi = d->ldi[0]; p.cin_pad = d->cin_pad; p.wp = d->w[0]; p.ntiles = d->ntiles; p.kgroups = kgroups;
+      p.bias = d->bias[0]; p.out = d->out[0]; p.ldo = d->ldo[0]; p.Bn = d->Bn; p.F = F; p.H = d->H; p.W = d->W;
+      p.kt = d->kt; p.relu = d->relu ? 1 : 0; p.wp3 = sc.p[0]; p.out_mode = d->out_mode; p.nout = d->out_mode ? d->nout : 0;
+      e = kdlae::launch_conv_lds(p, s);
+      break;
+    }
+    case 6: {  // small-output conv
+      if (!d->w[0]) return fail(KDLAE_EINVAL_CONFIG, null_op);
+      const int Cout = d->C2;
+      if (C < 16 || C % 16 || C > 4096 || Cout < 1 || Cout > 4 || (d->ks != 1 && d->ks != 3) || (d->wt && d->ks != 3))
+        return fail(KDLAE_EINVAL_SHAPE, "conv_small_out: Cin % 16 == 0, Cout 1 .. 4, ks 1 or 3 (wt: 3)");
+      if ((size_t)d->ks * d->ks * C * 16 > 65536) return fail(KDLAE_EINVAL_SHAPE, "conv_small_out: the weights must fit 64 KiB of LDS");
+      if (!geo || !in_ok(0, C, px) || !in4(0) || !d->out[0]) return fail(KDLAE_EINVAL_SHAPE, bad);
+      if (d->out_nchw) {
+        if (px * Cout >= kMaxIdx || d->R || d->in[2]) return fail(KDLAE_EINVAL_SHAPE, "conv_small_out: NCHW takes in1 = res only");
+      } else {
+        if (!out_ok(0, Cout + (d->in[2] ? 1 : 0), px) || d->in[1] || (d->R && (d->ldr < Cout || px * d->ldr >= kMaxIdx)))
+          return fail(KDLAE_EINVAL_SHAPE, "conv_small_out: NHWC takes R (ldr >= Cout) and in2 = extra (ldo > Cout)");
+      }
+      kdlae::SmallOutParams p{};
+      p.in = d->in[0]; p.ld = d->ldi[0]; p.Cin = C; p.Cout = Cout; p.w = d->w[0]; p.bias = d->bias[0];
+      p.Bn = d->Bn; p.H = d->H; p.W = d->W; p.F = F; p.ks = d->ks; p.out = d->out[0]; p.out_nchw = d->out_nchw ? 1 : 0;
+      p.ldo = d->ldo[0]; p.res = d->in[1]; p.extra = d->in[2]; p.wt = d->wt ? 1 : 0; p.res_nhwc = d->R; p.ldr = d->ldr;
+      e = kdlae::launch_conv_small_out(p, s);
+      break;
+    }
+    case 7: {  // 16 -> 16 channel conv
+      if (!d->w[0] || !d->bias[0]) return fail(KDLAE_EINVAL_CONFIG, null_op);
+      if (!geo || (d->kt != 1 && d->kt != 3) || !in_ok(0, 16, px) || !out_ok(0, 16, px)) return fail(KDLAE_EINVAL_SHAPE, bad);
+      if (!in4(0) || !out4(0) || !al16(d->w[0]) || !al16(d->bias[0])) return fail(KDLAE_EINVAL_SHAPE, align);
+      kdlae::Conv3dC16Params p{};
+      p.in = d->in[0]; p.ldi = d->ldi[0]; p.wp = d->w[0]; p.bias = d->bias[0]; p.out = d->out[0]; p.ldo = d->ldo[0];
+      p.Bn = d->Bn; p.F = F; p.H = d->H; p.W = d->W; p.relu = d->relu ? 1 : 0; p.kt = d->kt;
+      e = kdlae::launch_conv3d_c16(p, s);
+      break;
+    }
+    case 8: {  // max-pool 2x2 (floor), Bn frames
+      if (!geo || F != 1 || d->H < 2 || d->W < 2 || C < 4 || C % 4 || !in_ok(0, C, px) ||
+          !out_ok(0, C, (long long)d->Bn * (d->H / 2) * (d->W / 2)))
+        return fail(KDLAE_EINVAL_SHAPE, "maxpool2: C % 4 == 0, H, W >= 2");
+      if (!in4(0) || !out4(0)) return fail(KDLAE_EINVAL_SHAPE, align);
+      e = kdlae::launch_maxpool2(d->in[0], d->ldi[0], d->out[0], d->ldo[0], C, d->Bn, d->H, d->W, s);
+      break;
+    }
+    case 9: {  // global average pool partials + ASDQE head
+      for (int i = 0; i < 4; ++i)
+        if (!d->w[i] || !d->bias[i]) return fail(KDLAE_EINVAL_CONFIG, null_op);
+      if (!d->scratch || !d->out[0]) return fail(KDLAE_EINVAL_CONFIG, null_op);
+      if (!geo || F != 1 || d->Bn > 65535 || C < 4 || C % 4 || C > 1024 || d->slots < 1 || d->slots > 65535 || d->M < 1 ||
+          d->M > 1024 || d->N1 < 1 || d->N1 > 1024 || d->N2 < 1 || d->N2 > 1024 || !in_ok(0, C, px))
+        return fail(KDLAE_EINVAL_SHAPE, "gap + head: C % 4 == 0, C, M, N1, N2 <= 1024, slots >= 1");
+      if (!in4(0) || !al16(d->scratch)) return fail(KDLAE_EINVAL_SHAPE, align);
+      if ((long long)d->Bn * d->slots * C > d->scratch_floats)
+        return fail(KDLAE_EINVAL_SHAPE, "scratch must hold Bn * slots * C floats");
+      const long long HW = (long long)d->H * d->W;
+      e = kdlae::launch_gap_partial(d->in[0], d->ldi[0], C, d->Bn, HW, d->slots, d->scratch, s);
+      if (e != hipSuccess) break;
+      kdlae::HeadParams p{};
+      p.partial = d->scratch; p.slots = d->slots; p.C = C; p.inv_hw = 1.0f / (float)HW;
+      p.wo = d->w[0]; p.bo = d->bias[0]; p.M = d->M;
+      p.w1 = d->w[1]; p.b1 = d->bias[1]; p.N1 = d->N1;
+      p.w2 = d->w[2]; p.b2 = d->bias[2]; p.N2 = d->N2;
+      p.w3 = d->w[3]; p.b3 = d->bias[3];
+      p.score = d->out[0]; p.B = d->Bn;
+      e = kdlae::launch_asdqe_head(p, s);
+      break;
+    }
+    default: return fail(KDLAE_EINVAL_CONFIG, "op must be 0..9");
+  }
+  if (e != hipSuccess) return fail(KDLAE_EHIP, std::string("kdlae_debug_infer: ") + hipGetErrorString(e));
   return KDLAE_OK;
 }

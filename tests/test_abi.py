@@ -256,3 +256,85 @@ def test_debug_train_entries_refuse_bad_arguments():
     assert s(op=4, ins=[(P, 4), (P, 3)], out=P, ldo=4, C=4, **sg) == 1
     assert s(op=5, ins=[(P, 16), (P, 4)], out=P, ldo=4, C=4, B=1, F=1, H=3, W=4) == 1
     assert s(op=5, ins=[(P, 15), (P, 4)], out=P, ldo=4, C=4, **sg) == 1  # U narrower than 4 C
+
+
+# ------------------------------------------------------------------ inference-kernel self-test entry
+def test_debug_infer_entry_refuses_bad_arguments():
+    """kdlae_debug_infer checks every launcher precondition before it launches (1 = EINVAL_SHAPE,
+    2 = EINVAL_CONFIG).  The pointers here are never dereferenced."""
+    from rethink_acoustic_image_enhancement_amd._lib import InferDesc
+
+    L = _lib.lib()
+    P = 0x1000  # a non-null, 16-byte aligned "device pointer"
+
+    def f(ins=(), outs=(), w=(), bias=(), **kw):
+        d = InferDesc()
+        for i, (p, ld) in enumerate(ins):
+            d.inp[i], d.ldi[i] = p, ld
+        for i, (p, ld) in enumerate(outs):
+            d.out[i], d.ldo[i] = p, ld
+        for i, p in enumerate(w):
+            d.w[i] = p
+        for i, p in enumerate(bias):
+            d.bias[i] = p
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return L.kdlae_debug_infer(ctypes.byref(d), None)
+
+    geo = dict(Bn=2, H=8, W=16)
+    assert L.kdlae_debug_infer(None, None) == 2 and f(op=10, **geo) == 2 and f(op=-1, **geo) == 2
+    # gdfn: unsupported C / hidS, ld != 2 hidS, null zeros, misaligned residual, no geometry
+    g = dict(op=0, ins=[(P, 64)], outs=[(P, 48)], w=[P, P], zeros=P, C=48, hidS=32)
+    assert f(**{**g, "C": 64}, **geo) == 1 and f(**{**g, "hidS": 24}, **geo) == 1
+    assert f(**{**g, "hidS": 272, "ins": [(P, 544)]}, **geo) == 1      # C = 48 stops at 256
+    assert f(**{**g, "ins": [(P, 68)]}, **geo) == 1 and f(**{**g, "zeros": None}, **geo) == 2
+    assert f(**{**g, "outs": [(P, 44)]}, **geo) == 1 and f(**g, R=P + 4, ldr=48, **geo) == 1
+    assert f(**g, R=P, ldr=50, **geo) == 1 and f(**g, Bn=2, H=0, W=16) == 1
+    # ffn: odd chunk count, C = 48 past 8 chunks, ln, out overlapping x, ld % 4
+    h = dict(op=1, ins=[(P, 48)], outs=[(P + (1 << 20), 48)], w=[P, P, P], C=48, hidS=32, ln=1)
+    assert f(**{**h, "hidS": 48}, **geo) == 1 and f(**{**h, "hidS": 160}, **geo) == 1
+    assert f(**{**h, "ln": 0}, **geo) == 2 and f(**{**h, "w": [P, None, P]}, **geo) == 2
+    assert f(**{**h, "outs": [(P + 64, 48)]}, **geo) == 1 and "overlap" in _lib.last_error()
+    assert f(**{**h, "ins": [(P, 50)]}, **geo) == 1
+    # mdta_fused: W % 16, H % 8, segments that do not cover H / an empty one, scratch capacity
+    m = dict(op=2, ins=[(P, 48)], outs=[(P, 48), (P, 0)], w=[P, P], C=48, ln=2, nseg=1, seg_rows=8, scratch=P)
+    cap = 2 * 1 * (9 * 256 + 96)
+    assert f(**m, scratch_floats=cap, Bn=2, H=8, W=24) == 1 and f(**m, scratch_floats=cap, Bn=2, H=12, W=16) == 1
+    assert f(**{**m, "seg_rows": 8}, scratch_floats=cap, Bn=2, H=16, W=16) == 1
+    assert f(**{**m, "nseg": 3}, scratch_floats=3 * cap, Bn=2, H=16, W=16) == 1
+    assert f(**m, scratch_floats=cap - 1, **geo) == 1 and "scratch" in _lib.last_error()
+    assert f(**{**m, "C": 64}, scratch_floats=1 << 30, **geo) == 1
+    # attn_fold: Ch not a multiple of 16, Ch > 128, null temperature
+    a = dict(op=3, ins=[(P, 0)], outs=[(P, 0)], w=[P, P], Bn=2)
+    assert f(**a, C=48, heads=2) == 1 and f(**a, C=144, heads=1) == 1 and f(**a, C=40, heads=1) == 1
+    assert f(**{**a, "w": [P, None]}, C=48, heads=1) == 2
+    # dwconv_gate: hidS % 4, x narrower than 2 hidS, misaligned weights
+    q = dict(op=4, ins=[(P, 32)], outs=[(P, 16)], w=[P], hidS=16)
+    assert f(**{**q, "hidS": 6}, **geo) == 1 and f(**{**q, "ins": [(P, 28)]}, **geo) == 1
+    assert f(**{**q, "w": [P + 8]}, **geo) == 1 and f(**{**q, "outs": [(P, 12)]}, **geo) == 1
+    # conv_lds: tile count, cin_pad, the store geometry of each mode, tap-pair records without their block
+    c = dict(op=5, ins=[(P, 16)], outs=[(P, 32)], w=[P], ntiles=2, cin_pad=16, kt=1)
+    assert f(**{**c, "ntiles": 1}, **geo) == 1 and f(**{**c, "ntiles": 17}, **geo) == 1
+    assert f(**{**c, "cin_pad": 24}, **geo) == 1 and f(**{**c, "ins": [(P, 12)]}, **geo) == 1
+    assert f(**{**c, "outs": [(P, 28)]}, **geo) == 1 and f(**{**c, "kt": 2}, **geo) == 1
+    assert f(**c, out_mode=1, nout=24, Bn=2, H=7, W=16) == 1 and f(**c, out_mode=1, nout=24, **geo) == 1  # ldo < 4 nout
+    assert f(**c, out_mode=2, nout=22, **geo) == 1 and f(**c, out_mode=2, nout=36, **geo) == 1
+    assert f(**c, out_mode=3, nout=4, **geo) == 1 and f(**{**c, "kt": 3}, use_wp3=1, F=3, **geo) == 2
+    assert f(**{**c, "kt": 3}, out_mode=1, nout=8, F=3, **geo) == 1
+    # conv_small_out: Cin % 16 (both kernels move 16 channels a step), Cout, ks, wt, operands per layout
+    s = dict(op=6, ins=[(P, 48)], outs=[(P, 4)], w=[P], C=48, C2=3, ks=3)
+    assert f(**{**s, "C": 20}, **geo) == 1 and f(**{**s, "C": 36}, **geo) == 1 and "Cin % 16" in _lib.last_error()
+    assert f(**{**s, "C2": 5}, **geo) == 1 and f(**{**s, "ks": 2}, **geo) == 1 and f(**{**s, "ks": 1}, wt=1, **geo) == 1
+    assert f(**{**s, "ins": [(P, 50)]}, **geo) == 1 and f(**{**s, "outs": [(P, 2)]}, **geo) == 1
+    assert f(**{**s, "ins": [(P, 48), (None, 0), (P, 0)], "outs": [(P, 3)]}, **geo) == 1   # extra needs ldo > Cout
+    assert f(**s, out_nchw=1, R=P, ldr=4, **geo) == 1 and f(**s, R=P, ldr=2, **geo) == 1
+    # conv3d_c16, maxpool2, gap + head
+    assert f(op=7, ins=[(P, 12)], outs=[(P, 16)], w=[P], bias=[P], kt=3, F=2, **geo) == 1
+    assert f(op=7, ins=[(P, 16)], outs=[(P, 16)], w=[P], bias=[P], kt=2, **geo) == 1
+    assert f(op=7, ins=[(P, 16)], outs=[(P, 16)], w=[P], kt=1, **geo) == 2
+    assert f(op=8, ins=[(P, 8)], outs=[(P, 8)], C=6, **geo) == 1 and f(op=8, ins=[(P, 8)], outs=[(P, 8)], C=8, Bn=1, H=1, W=4) == 1
+    assert f(op=8, ins=[(P, 10)], outs=[(P, 8)], C=8, **geo) == 1
+    hd = dict(op=9, ins=[(P, 64)], outs=[(P, 0)], w=[P] * 4, bias=[P] * 4, scratch=P, C=64, slots=7, M=96, N1=256, N2=64)
+    assert f(**hd, scratch_floats=2 * 7 * 64 - 1, **geo) == 1 and f(**{**hd, "N1": 1025}, scratch_floats=1 << 20, **geo) == 1
+    assert f(**{**hd, "slots": 0}, scratch_floats=1 << 20, **geo) == 1
+    assert f(**{**hd, "bias": [P, P, P, None]}, scratch_floats=1 << 20, **geo) == 2
