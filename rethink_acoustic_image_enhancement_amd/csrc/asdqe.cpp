@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "param_layout.h"
 #include "runtime.h"
 
 using namespace kdlae;
@@ -49,15 +50,9 @@ int gap_slots(long long HW) {
   return (int)std::max<long long>(1, std::min<long long>(256, s));
 }
 
-struct APlan {
-  size_t total = 0;
+struct APlan : WsPlan {
   size_t e1, merged, t0, cat3, y3, p1, t1, cat2, y2, p2, t2, cat1, y1, p3, t3, x4, partial;
   int Hp, Wp, slots;
-  size_t take(long long floats) {
-    size_t off = total;
-    total += ((size_t)floats * 4 + 255) / 256 * 256;
-    return off;
-  }
 };
 
 APlan make_aplan(const asdqe_handle* h, int B, int H, int W) {
@@ -101,30 +96,7 @@ int asdqe_create(const asdqe_config* cfg, int device, asdqe_handle** out) {
   auto* h = new asdqe_handle();
   h->cfg = *cfg;
   h->device = device;
-  // state_dict keys in registration order (ASDQE_model.py:127-156), BN buffers included
-  auto dc = [&](const std::string& p, int cin, int cout) {
-    for (int i : {0, 3}) {
-      const int ci = i == 0 ? cin : cout;
-      h->ps.add(p + "." + std::to_string(i) + ".weight", (int64_t)cout * ci * 9);
-      h->ps.add(p + "." + std::to_string(i) + ".bias", cout);
-      const std::string bn = p + "." + std::to_string(i + 1) + ".";
-      for (const char* s : {"weight", "bias", "running_mean", "running_var"}) h->ps.add(bn + s, cout);
-      h->ps.add(bn + "num_batches_tracked", 1);
-    }
-  };
-  const int d = cfg->dim, m = 3 * d;
-  for (const char* e : kExt) dc(std::string(e) + ".double_conv", cfg->in_channels, d);
-  dc("unet.inc.double_conv", m, 64);
-  for (int i = 0; i < 3; ++i) dc(kDown[i], kDownC[i][0], kDownC[i][1]);
-  for (int i = 0; i < 3; ++i) dc(kUp[i], kUpC[i][0], kUpC[i][1]);
-  h->ps.add("unet.outc.conv.weight", (int64_t)m * 64);
-  h->ps.add("unet.outc.conv.bias", m);
-  h->ps.add("regressor.2.weight", (int64_t)256 * m);
-  h->ps.add("regressor.2.bias", 256);
-  h->ps.add("regressor.5.weight", 256 * 64);
-  h->ps.add("regressor.5.bias", 64);
-  h->ps.add("regressor.8.weight", 64);
-  h->ps.add("regressor.8.bias", 1);
+  asdqe_keys(*cfg, true, h->ps.lay);  // state_dict order, BN buffers included
   *out = h;
   return KDLAE_OK;
 }
@@ -139,14 +111,14 @@ int asdqe_destroy(asdqe_handle* h) {
   return KDLAE_OK;
 }
 
-int asdqe_num_params(const asdqe_handle* h) { return h ? (int)h->ps.keys.size() : 0; }
+int asdqe_num_params(const asdqe_handle* h) { return h ? (int)h->ps.lay.size() : 0; }
 
 int asdqe_param_info(const asdqe_handle* h, int index, const char** name, int64_t* numel) {
   if (!h) return fail(KDLAE_ESTATE, "null handle");
-  return h->ps.info(index, name, numel);
+  return h->ps.lay.info(index, name, numel, nullptr);
 }
 
-int64_t asdqe_params_numel(const asdqe_handle* h) { return h ? h->ps.total : -1; }
+int64_t asdqe_params_numel(const asdqe_handle* h) { return h ? h->ps.lay.total : -1; }
 
 int asdqe_set_param(asdqe_handle* h, const char* name, const float* host_data, int64_t numel) {
   if (!h || !name || !host_data) return fail(KDLAE_ESTATE, "null argument");
@@ -159,7 +131,7 @@ int asdqe_set_param(asdqe_handle* h, const char* name, const float* host_data, i
 static int build_program_a(asdqe_handle* h) {
   if (h->built) return KDLAE_OK;
   PackProgram ar;
-  ar.nsrc = h->ps.total;
+  ar.nsrc = h->ps.lay.total;
   int err = KDLAE_OK;
   // BatchNorm2d eval (eps 1e-5) folded into the preceding conv: W' = s W, b' = s (b - rm) + beta,
   // s = gamma / sqrt(rv + eps): s and b' are derived values computed on the device before the gathers
@@ -302,9 +274,9 @@ int asdqe_prepare(asdqe_handle* h) {
 
 int asdqe_pack_device(asdqe_handle* h, const float* params, int64_t numel, void* stream) {
   if (!h) return fail(KDLAE_ESTATE, "null handle");
-  if (numel != h->ps.total)
+  if (numel != h->ps.lay.total)
     return fail(KDLAE_EPARAM, "flat parameter vector has " + std::to_string(numel) + " floats, expected " +
-                                  std::to_string(h->ps.total));
+                                  std::to_string(h->ps.lay.total));
   int rc = build_program_a(h);
   if (rc) return rc;
   DeviceGuard g(h->device);

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "param_layout.h"
 #include "runtime.h"
 #include "train_a.h"
 #include "train_kernels.h"
@@ -34,10 +35,8 @@ namespace tr = kdlae::train;
 struct asdqe_train_handle {
   asdqe_config cfg{};
   int device = 0;
-  std::vector<std::string> names;
-  std::vector<int64_t> numel, offset;
-  std::unordered_map<std::string, int64_t> off;
-  int64_t total = 0, nstat = 0;
+  ParamLayout lay{4};  // named_parameters() order, every key 16-byte aligned
+  int64_t nstat = 0;   // floats of the statistics buffer: every BatchNorm's running_mean | running_var
   // the last forward (its activations live in the caller's workspace)
   bool valid = false;
   int B = 0, H = 0, W = 0;
@@ -64,8 +63,7 @@ struct Layer {
   int64_t run = 0;  // offset of [running_mean | running_var] in the statistics buffer
 };
 
-struct TPlan {
-  size_t total = 0;
+struct TPlan : WsPlan {
   int Hp = 0, Wp = 0, slots = 1;
   long long P[4] = {0, 0, 0, 0};
   std::vector<Layer> L;
@@ -73,11 +71,6 @@ struct TPlan {
   size_t ga[4] = {0, 0, 0, 0}, gb[4] = {0, 0, 0, 0}, dcat3 = 0, dcat2 = 0, dcat1 = 0, gmerged = 0, ge1 = 0;
   size_t gap = 0, save = 0, m1 = 0, m2 = 0, wpk = 0, partial = 0, part = 0, dw4 = 0, gtmp = 0;
   long long max_elems = 0;  // the largest view (pixels x pixel stride) any kernel indexes
-  size_t take(long long floats) {
-    const size_t o = total;
-    total += ((size_t)floats * 4 + 255) / 256 * 256;
-    return o;
-  }
 };
 
 int gap_slots(long long HW) { return (int)std::max<long long>(1, std::min<long long>(256, HW / 2048)); }
@@ -157,7 +150,7 @@ TPlan make_plan(const asdqe_train_handle* h, int B, int H, int W) {
   pl.partial = pl.take((long long)kPartialFloats);
   pl.part = pl.take((long long)kPartFloats);
   pl.dw4 = pl.take(256LL * 4 * 9);
-  pl.gtmp = pl.take(h->total);
+  pl.gtmp = pl.take(h->lay.total);
   return pl;
 }
 
@@ -170,24 +163,15 @@ struct Ctx {
   hipStream_t s;
   int B;
   float* buf(size_t o) const { return reinterpret_cast<float*>(ws + o); }
-  const float* P(const std::string& k) const { return th + h->off.at(k); }
-  float* G(const std::string& k) const { return gr + h->off.at(k); }
+  const float* P(const std::string& k) const { return th + h->lay.at(k); }
+  float* G(const std::string& k) const { return gr + h->lay.at(k); }
 };
 
-#define TRY(x)           \
-  do {                   \
-    int rc_ = (x);       \
-    if (rc_) return rc_; \
-  } while (0)
-
-// the implicit-GEMM 3x3 conv's B operand as a [9 Cg][N] matrix (bmode 2 / 3 -> 0), as kdlae_train.cpp
+// the implicit-GEMM 3x3 conv's B operand as a [9 Cg][N] matrix (bmode 2 / 3 -> 0)
 int pack_w3(Ctx& c, tr::TGemm& g, int N) {
   float* wp = c.buf(c.pl.wpk);
   HIPCHK(tr::launch_pack_w3(g.B, g.Cg, N, g.bmode, wp, c.s));
-  g.B = wp;
-  g.bmode = 0;
-  g.sbk = N;
-  g.sbn = 1;
+  tr::use_packed_w3(g, wp, N);
   return KDLAE_OK;
 }
 
@@ -428,41 +412,7 @@ int asdqe_train_create(const asdqe_config* cfg, int device, asdqe_train_handle**
   auto* h = new asdqe_train_handle();
   h->cfg = *cfg;
   h->device = device;
-  auto add = [&](const std::string& k, int64_t n) {
-    h->names.push_back(k);
-    h->numel.push_back(n);
-    h->offset.push_back(h->total);
-    h->off[k] = h->total;
-    h->total += (n + 3) / 4 * 4;  // 16-byte aligned keys (pads stay zero)
-  };
-  // named_parameters() order (ASDQE_model.py:127-156); the BatchNorm buffers live in the statistics buffer
-  auto dc = [&](const std::string& p, int cin, int cout) {
-    for (int i : {0, 3}) {
-      const int ci = i == 0 ? cin : cout;
-      add(p + "." + std::to_string(i) + ".weight", (int64_t)cout * ci * 9);
-      add(p + "." + std::to_string(i) + ".bias", cout);
-      add(p + "." + std::to_string(i + 1) + ".weight", cout);
-      add(p + "." + std::to_string(i + 1) + ".bias", cout);
-      h->nstat += 2 * cout;
-    }
-  };
-  const int d = cfg->dim, m = 3 * d;
-  for (const char* e : kExt) dc(std::string(e) + ".double_conv", cfg->in_channels, d);
-  dc("unet.inc.double_conv", m, 64);
-  dc("unet.down1.maxpool_conv.1.double_conv", 64, 128);
-  dc("unet.down2.maxpool_conv.1.double_conv", 128, 256);
-  dc("unet.down3.maxpool_conv.1.double_conv", 256, 256);
-  dc("unet.up1.conv.double_conv", 512, 128);
-  dc("unet.up2.conv.double_conv", 256, 64);
-  dc("unet.up3.conv.double_conv", 128, 64);
-  add("unet.outc.conv.weight", (int64_t)m * 64);
-  add("unet.outc.conv.bias", m);
-  add("regressor.2.weight", (int64_t)kN1 * m);
-  add("regressor.2.bias", kN1);
-  add("regressor.5.weight", kN1 * kN2);
-  add("regressor.5.bias", kN2);
-  add("regressor.8.weight", kN2);
-  add("regressor.8.bias", 1);
+  h->nstat = asdqe_keys(*cfg, false, h->lay);  // the BatchNorm buffers live in the statistics buffer
   *out = h;
   return KDLAE_OK;
 }
@@ -472,17 +422,14 @@ int asdqe_train_destroy(asdqe_train_handle* h) {
   return KDLAE_OK;
 }
 
-int asdqe_train_num_params(const asdqe_train_handle* h) { return h ? (int)h->names.size() : -1; }
+int asdqe_train_num_params(const asdqe_train_handle* h) { return h ? h->lay.size() : -1; }
 
 int asdqe_train_param_info(const asdqe_train_handle* h, int i, const char** name, int64_t* numel, int64_t* offset) {
-  if (!h || i < 0 || i >= (int)h->names.size()) return fail(KDLAE_EPARAM, "param index out of range");
-  if (name) *name = h->names[i].c_str();
-  if (numel) *numel = h->numel[i];
-  if (offset) *offset = h->offset[i];
-  return KDLAE_OK;
+  if (!h) return fail(KDLAE_EPARAM, "param index out of range");
+  return h->lay.info(i, name, numel, offset);
 }
 
-int64_t asdqe_train_num_floats(const asdqe_train_handle* h) { return h ? h->total : -1; }
+int64_t asdqe_train_num_floats(const asdqe_train_handle* h) { return h ? h->lay.total : -1; }
 int64_t asdqe_train_num_stat_floats(const asdqe_train_handle* h) { return h ? h->nstat : -1; }
 
 int64_t asdqe_train_workspace_bytes(const asdqe_train_handle* h, int B, int H, int W) {
@@ -535,10 +482,10 @@ int asdqe_train_backward(asdqe_train_handle* h, const float* theta, const float*
   DeviceGuard dg(h->device);
   c.gr = c.buf(c.pl.gtmp);
   // zero: the pad floats and the BatchNorm-fed conv biases, whose gradient is exactly zero
-  HIPCHK(hipMemsetAsync(c.gr, 0, (size_t)h->total * sizeof(float), c.s));
+  HIPCHK(hipMemsetAsync(c.gr, 0, (size_t)h->lay.total * sizeof(float), c.s));
   h->valid = false;  // a forward's activations serve one backward
   TRY(net_bwd(c, dscore));
-  HIPCHK(tr::launch_grad_commit(c.gr, grad, h->total, accumulate ? 1 : 0, c.s));
+  HIPCHK(tr::launch_grad_commit(c.gr, grad, h->lay.total, accumulate ? 1 : 0, c.s));
   return KDLAE_OK;
 }
 

@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "param_layout.h"
 #include "runtime.h"
 
 using namespace kdlae;
@@ -38,15 +39,9 @@ struct kdlae_s_handle {
 
 namespace {
 
-struct SPlan {
-  size_t total = 0;
+struct SPlan : WsPlan {
   std::vector<size_t> skip;
   size_t tA = 0, tB = 0;
-  size_t take(long long floats) {
-    size_t off = total;
-    total += ((size_t)floats * 4 + 255) / 256 * 256;
-    return off;
-  }
 };
 
 SPlan make_splan(const kdlae_s_handle* h, int B, int F, int H, int W) {
@@ -91,29 +86,7 @@ int kdlae_s_create(const kdlae_s_config* cfg, int device, kdlae_s_handle** out) 
     h->hc.push_back(cfg->hidden_channels[i]);
     h->cs.push_back(ru16(cfg->hidden_channels[i]));
   }
-  // state_dict keys in registration order (KDLAE_model.py:359-384)
-  auto blk = [&](const std::string& p, int cin, int cout) {
-    h->ps.add(p + ".0.weight", (int64_t)cout * cin * 27);
-    h->ps.add(p + ".0.bias", cout);
-    h->ps.add(p + ".2.weight", (int64_t)cout * cout * 27);
-    h->ps.add(p + ".2.bias", cout);
-  };
-  int cin = cfg->inp_channels;
-  for (int i = 0; i < h->L; ++i) {
-    blk("encoders." + std::to_string(i), cin, h->hc[i]);
-    cin = h->hc[i];
-  }
-  blk("st_fusion", cin, h->hc[h->L]);
-  for (int j = 0, i = h->L - 1; i >= 0; --i, ++j) {
-    const int cu = (i == h->L - 1) ? h->hc[h->L] : h->hc[i + 1];
-    h->ps.add("upconv_layers." + std::to_string(j) + ".weight", (int64_t)cu * h->hc[i] * 4);
-    h->ps.add("upconv_layers." + std::to_string(j) + ".bias", h->hc[i]);
-  }
-  for (int j = 0, i = h->L - 1; i >= 0; --i, ++j) blk("decoders." + std::to_string(j), h->hc[i], h->hc[i]);
-  h->ps.add("out_conv.weight", (int64_t)cfg->out_channels * h->hc[0]);
-  h->ps.add("out_conv.bias", cfg->out_channels);
-  // the reference registers encoders, pooling, st_fusion, upconv_layers, decoders, out_conv in that
-  // attribute order; state_dict() lists encoders.*, st_fusion.*, upconv_layers.*, decoders.*, out_conv.*
+  student_keys(*cfg, h->ps.lay);
   *out = h;
   return KDLAE_OK;
 }
@@ -128,14 +101,14 @@ int kdlae_s_destroy(kdlae_s_handle* h) {
   return KDLAE_OK;
 }
 
-int kdlae_s_num_params(const kdlae_s_handle* h) { return h ? (int)h->ps.keys.size() : 0; }
+int kdlae_s_num_params(const kdlae_s_handle* h) { return h ? (int)h->ps.lay.size() : 0; }
 
 int kdlae_s_param_info(const kdlae_s_handle* h, int index, const char** name, int64_t* numel) {
   if (!h) return fail(KDLAE_ESTATE, "null handle");
-  return h->ps.info(index, name, numel);
+  return h->ps.lay.info(index, name, numel, nullptr);
 }
 
-int64_t kdlae_s_params_numel(const kdlae_s_handle* h) { return h ? h->ps.total : -1; }
+int64_t kdlae_s_params_numel(const kdlae_s_handle* h) { return h ? h->ps.lay.total : -1; }
 
 int kdlae_s_set_param(kdlae_s_handle* h, const char* name, const float* host_data, int64_t numel) {
   if (!h || !name || !host_data) return fail(KDLAE_ESTATE, "null argument");
@@ -148,7 +121,7 @@ int kdlae_s_set_param(kdlae_s_handle* h, const char* name, const float* host_dat
 static int build_program_s(kdlae_s_handle* h) {
   if (h->built) return KDLAE_OK;
   PackProgram ar;
-  ar.nsrc = h->ps.total;
+  ar.nsrc = h->ps.lay.total;
   int err = KDLAE_OK;
   auto conv3d = [&](const std::string& name, int cin, int cout) {
     const int32_t W = h->ps.base(name + ".weight", &err);
@@ -290,9 +263,9 @@ int kdlae_s_prepare(kdlae_s_handle* h) {
 
 int kdlae_s_pack_device(kdlae_s_handle* h, const float* params, int64_t numel, void* stream) {
   if (!h) return fail(KDLAE_ESTATE, "null handle");
-  if (numel != h->ps.total)
+  if (numel != h->ps.lay.total)
     return fail(KDLAE_EPARAM, "flat parameter vector has " + std::to_string(numel) + " floats, expected " +
-                                  std::to_string(h->ps.total));
+                                  std::to_string(h->ps.lay.total));
   int rc = build_program_s(h);  // no-op after kdlae_s_prepare
   if (rc) return rc;
   DeviceGuard g(h->device);

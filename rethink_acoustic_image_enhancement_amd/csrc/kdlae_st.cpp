@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "param_layout.h"
 #include "runtime.h"
 #include "train_kernels.h"
 #include "train_s.h"
@@ -32,10 +33,7 @@ struct kdlae_st_handle {
   int device = 0;
   int L = 0;
   std::vector<int> hc;
-  std::vector<std::string> names;
-  std::vector<int64_t> numel, offset;
-  std::unordered_map<std::string, int64_t> off;
-  int64_t total = 0;
+  ParamLayout lay{4};  // state_dict order, every key 16-byte aligned
   // the last forward (its activations live in the caller's workspace)
   bool valid = false;
   int B = 0, F = 0, H = 0, W = 0;
@@ -59,17 +57,11 @@ constexpr auto KDLAE_ST_DX_CONV = 1;
 constexpr auto KDLAE_ST_DIRECT = 1;
 constexpr int kColsumBlocks = 256;
 
-struct SPlanT {
-  size_t total = 0;
+struct SPlanT : WsPlan {
   std::vector<size_t> ea, e, pool, ua, da, dd, dl, gskip;  // per level / decoder
   std::unordered_map<std::string, size_t> xcol;            // each Conv3d's forward column matrix
   size_t fa = 0, fo = 0, col = 0, gA = 0, gB = 0, partial = 0, part = 0, wp = 0, dwp = 0, wpk = 0, zb = 0;
   long long col2im_max = 0;  // the largest P * cin a col2im gathers (its element index is 32-bit)
-  size_t take(long long floats) {
-    const size_t o = total;
-    total += ((size_t)floats * 4 + 255) / 256 * 256;
-    return o;
-  }
 };
 
 long long npx(const kdlae_st_handle* h, int lvl, int B, int F, int H, int W) {
@@ -167,15 +159,9 @@ struct Ctx {
   hipStream_t side = nullptr;    // set by the backward unless KDLAE_DEBUG=train_serial
   hipStream_t main_s = nullptr;  // the caller's stream (c.s is the side stream inside a side segment)
   float* buf(size_t o) const { return reinterpret_cast<float*>(ws + o); }
-  const float* P(const std::string& k) const { return th + h->off.at(k); }
-  float* G(const std::string& k) const { return gr + h->off.at(k); }
+  const float* P(const std::string& k) const { return th + h->lay.at(k); }
+  float* G(const std::string& k) const { return gr + h->lay.at(k); }
 };
-
-#define TRY(x)                   \
-  do {                           \
-    int rc_ = (x);               \
-    if (rc_) return rc_;         \
-  } while (0)
 
 int gemm(Ctx& c, tr::TGemm g, bool split) {
   if (split) {
@@ -473,33 +459,7 @@ int kdlae_st_create(const kdlae_s_config* cfg, int device, kdlae_st_handle** out
     }
     h->hc.push_back(cfg->hidden_channels[i]);
   }
-  auto add = [&](const std::string& k, int64_t n) {
-    h->names.push_back(k);
-    h->numel.push_back(n);
-    h->offset.push_back(h->total);
-    h->off[k] = h->total;
-    h->total += (n + 3) / 4 * 4;  // 16-byte aligned keys (pads stay zero)
-  };
-  auto blk = [&](const std::string& p, int cin, int cout) {
-    add(p + ".0.weight", (int64_t)cout * cin * 27);
-    add(p + ".0.bias", cout);
-    add(p + ".2.weight", (int64_t)cout * cout * 27);
-    add(p + ".2.bias", cout);
-  };
-  int cin = 1;
-  for (int i = 0; i < h->L; ++i) {
-    blk("encoders." + std::to_string(i), cin, h->hc[i]);
-    cin = h->hc[i];
-  }
-  blk("st_fusion", cin, h->hc[h->L]);
-  for (int j = 0, i = h->L - 1; i >= 0; --i, ++j) {
-    const int cu = (i == h->L - 1) ? h->hc[h->L] : h->hc[i + 1];
-    add("upconv_layers." + std::to_string(j) + ".weight", (int64_t)cu * h->hc[i] * 4);
-    add("upconv_layers." + std::to_string(j) + ".bias", h->hc[i]);
-  }
-  for (int j = 0, i = h->L - 1; i >= 0; --i, ++j) blk("decoders." + std::to_string(j), h->hc[i], h->hc[i]);
-  add("out_conv.weight", h->hc[0]);
-  add("out_conv.bias", 1);
+  student_keys(*cfg, h->lay);
   *out = h;
   return KDLAE_OK;
 }
@@ -509,17 +469,14 @@ int kdlae_st_destroy(kdlae_st_handle* h) {
   return KDLAE_OK;
 }
 
-int kdlae_st_num_params(const kdlae_st_handle* h) { return h ? (int)h->names.size() : -1; }
+int kdlae_st_num_params(const kdlae_st_handle* h) { return h ? h->lay.size() : -1; }
 
 int kdlae_st_param_info(const kdlae_st_handle* h, int i, const char** name, int64_t* numel, int64_t* offset) {
-  if (!h || i < 0 || i >= (int)h->names.size()) return fail(KDLAE_EPARAM, "param index out of range");
-  if (name) *name = h->names[i].c_str();
-  if (numel) *numel = h->numel[i];
-  if (offset) *offset = h->offset[i];
-  return KDLAE_OK;
+  if (!h) return fail(KDLAE_EPARAM, "param index out of range");
+  return h->lay.info(i, name, numel, offset);
 }
 
-int64_t kdlae_st_num_floats(const kdlae_st_handle* h) { return h ? h->total : -1; }
+int64_t kdlae_st_num_floats(const kdlae_st_handle* h) { return h ? h->lay.total : -1; }
 
 int64_t kdlae_st_workspace_bytes(const kdlae_st_handle* h, int B, int F, int H, int W) {
   if (!h) return -1;
@@ -576,7 +533,7 @@ int kdlae_st_backward(kdlae_st_handle* h, const float* theta, const float* dout,
     }
     c.side = h->side;
   }
-  HIPCHK(hipMemsetAsync(grad, 0, (size_t)h->total * sizeof(float), c.s));  // the pad floats stay zero
+  HIPCHK(hipMemsetAsync(grad, 0, (size_t)h->lay.total * sizeof(float), c.s));  // the pad floats stay zero
   HIPCHK(hipMemsetAsync(c.buf(c.pl.zb), 0, 64 * sizeof(float), c.s));
   return net_bwd(c, h->x, dout);
 }

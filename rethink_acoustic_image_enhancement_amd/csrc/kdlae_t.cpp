@@ -21,6 +21,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "param_layout.h"
 #include "runtime.h"
 
 namespace kdlae {
@@ -78,69 +79,6 @@ struct kdlae_t_handle {
 };
 
 namespace kdlae {
-
-static int hid_of(const kdlae_t_config& c, int dim) { return (int)((double)dim * c.ffn_expansion_factor); }
-
-static void add_key(kdlae_t_handle* h, const std::string& k, int64_t n) { h->ps.add(k, n); }
-
-// Expected state_dict (KDLAE_model.py:220-268, TransformerBlock :150-157, Attention :113-120,
-// FeedForward :90-99, LayerNorm :73-79).
-static void build_keys(kdlae_t_handle* h) {
-  const kdlae_t_config& c = h->cfg;
-  auto conv = [&](const std::string& n, int co, int ci, int k, bool b) {
-    add_key(h, n + ".weight", (int64_t)co * ci * k * k);
-    if (b) add_key(h, n + ".bias", co);
-  };
-  auto block = [&](const std::string& p, int dim, int heads) {
-    const int hid = hid_of(c, dim);
-    add_key(h, p + ".norm1.body.weight", dim);
-    if (!c.layernorm_biasfree) add_key(h, p + ".norm1.body.bias", dim);
-    add_key(h, p + ".attn.temperature", heads);
-    conv(p + ".attn.qkv", 3 * dim, dim, 1, c.bias);
-    conv(p + ".attn.qkv_dwconv", 3 * dim, 1, 3, c.bias);
-    conv(p + ".attn.project_out", dim, dim, 1, c.bias);
-    add_key(h, p + ".norm2.body.weight", dim);
-    if (!c.layernorm_biasfree) add_key(h, p + ".norm2.body.bias", dim);
-    conv(p + ".ffn.project_in", 2 * hid, dim, 1, c.bias);
-    conv(p + ".ffn.dwconv", 2 * hid, 1, 3, c.bias);
-    conv(p + ".ffn.project_out", dim, hid, 1, c.bias);
-  };
-  auto stage = [&](const std::string& n, int cnt, int dim, int heads) {
-    for (int i = 0; i < cnt; ++i) block(n + "." + std::to_string(i), dim, heads);
-  };
-  const int d = c.dim;
-  const int* nb = c.num_blocks;
-  const int* hd = c.heads;
-  const int nr = c.num_refinement_blocks;
-  conv("patch_embed.proj", d, c.inp_channels, 3, false);
-  stage("encoder_level1", nb[0], d, hd[0]);
-  conv("down1_2.body.0", d / 2, d, 3, false);
-  stage("encoder_level2", nb[1], 2 * d, hd[1]);
-  conv("down2_3.body.0", d, 2 * d, 3, false);
-  stage("encoder_level3", nb[2], 4 * d, hd[2]);
-  conv("down3_4.body.0", 2 * d, 4 * d, 3, false);
-  stage("latent", nb[3], 8 * d, hd[3]);
-  conv("up4_3.body.0", 16 * d, 8 * d, 3, false);
-  conv("reduce_chan_level3", 4 * d, 8 * d, 1, c.bias);
-  stage("decoder_level3", nb[2], 4 * d, hd[2]);
-  conv("up3_2.body.0", 8 * d, 4 * d, 3, false);
-  conv("reduce_chan_level2", 2 * d, 4 * d, 1, c.bias);
-  stage("decoder_level2", nb[1], 2 * d, hd[1]);
-  conv("up2_1.body.0", 4 * d, 2 * d, 3, false);
-  stage("decoder_level1", nb[0], 2 * d, hd[0]);
-  stage("refinement", nr, 2 * d, hd[0]);
-  conv("output", c.out_channels, 2 * d, 3, c.bias);
-  conv("output_param", 2 * d, c.out_channels + 1, 3, c.bias);
-  stage("refinement_out", nr, 2 * d, hd[0]);
-  conv("output2", c.out_channels, 2 * d, 3, c.bias);
-  if (c.static_train) {
-    const int hc = 2 * d;
-    conv("cen", hc, c.out_channels, 3, c.bias);
-    conv("upen.body.0", 2 * hc, hc, 3, false);
-    stage("enhance", nr, hc / 2, hd[0]);
-    conv("outputen", c.out_channels, hc / 2, 3, c.bias);
-  }
-}
 
 static int validate(const kdlae_t_config& c) {
   if (c.dual_pixel_task)
@@ -400,15 +338,9 @@ struct Packer {
 };
 
 // ----------------------------------------------------------------------------- workspace plan
-struct Plan {
-  size_t total = 0;
+struct Plan : WsPlan {
   size_t catL1, catL2, catL3, lat, dec3, dec2, out4, refo, cenb, srs;
   size_t qkv, vbuf, fpre, fg, stats, part, red, Mp;
-  size_t take(size_t floats) {
-    size_t off = total;
-    total += (floats * 4 + 255) / 256 * 256;
-    return off;
-  }
 };
 
 // Partial Gram slots per (image, head).  The slot partition depends on the image size only, never on
@@ -420,7 +352,7 @@ struct Plan {
 constexpr auto KDLAE_T_DOWN_LDS = 1;  // Downsample convs on conv_lds (0: the implicit GEMM)
 constexpr auto KDLAE_T_UP_LDS = 1;  // Upsample convs on conv_lds (0: the implicit GEMM)
 constexpr int kGramMaxSeg = 8, kGramMinRows = 32;  // Gram slots: row segments per strip, rows per segment
-static int nslots_for(int H, int W, int /*B*/, int /*heads*/) {
+int nslots_for(int H, int W) {
   if (W % 16 == 0) {
     const int strips = W / 16;
     const int nseg = std::max(1, std::min(kGramMaxSeg, (H + kGramMinRows - 1) / kGramMinRows));
@@ -457,7 +389,7 @@ static Plan make_plan(const kdlae_t_handle* h, int B, int H, int W) {
       mfp = std::max(mfp, P * 2 * b.hidS);
       if (!b.fused_gdfn) mfg = std::max(mfg, P * b.hidS);  // gated tensor: unfused FFN tails only
       mst = std::max(mst, P * 2);
-      mpart = std::max(mpart, (long long)B * b.heads * nslots_for(Hh, Ww, B, b.heads) * slot);
+      mpart = std::max(mpart, (long long)B * b.heads * nslots_for(Hh, Ww) * slot);
       mred = std::max(mred, (long long)B * b.heads * slot);
       mM = std::max(mM, (long long)B * split3_floats(b.C / 16, b.C / 16));
     }
@@ -592,7 +524,7 @@ struct Fwd {
     const long long P = (long long)B * HW;
     int rc;
     // --- attention
-    const int nslots = nslots_for(Hh, Ww, B, b.heads);
+    const int nslots = nslots_for(Hh, Ww);
     const int nseg = Ww % 16 == 0 ? nslots / (Ww / 16) : 0;
     const int seg_rows = nseg ? (Hh + nseg - 1) / nseg : 0;
     if (b.mdta_fused && mdta_fused_supported(b.C, b.heads, Hh, Ww, nseg, seg_rows)) {
@@ -931,7 +863,7 @@ int kdlae_t_create(const kdlae_t_config* cfg, int device, kdlae_t_handle** out) 
   auto* h = new kdlae_t_handle();
   h->cfg = *cfg;
   h->device = device;
-  build_keys(h);
+  teacher_keys(h->cfg, h->ps.lay);
   *out = h;
   return KDLAE_OK;
 }
@@ -947,14 +879,14 @@ int kdlae_t_destroy(kdlae_t_handle* h) {
   return KDLAE_OK;
 }
 
-int kdlae_t_num_params(const kdlae_t_handle* h) { return h ? (int)h->ps.keys.size() : 0; }
+int kdlae_t_num_params(const kdlae_t_handle* h) { return h ? (int)h->ps.lay.size() : 0; }
 
 int kdlae_t_param_info(const kdlae_t_handle* h, int index, const char** name, int64_t* numel) {
   if (!h) return fail(KDLAE_ESTATE, "null handle");
-  return h->ps.info(index, name, numel);
+  return h->ps.lay.info(index, name, numel, nullptr);
 }
 
-int64_t kdlae_t_params_numel(const kdlae_t_handle* h) { return h ? h->ps.total : -1; }
+int64_t kdlae_t_params_numel(const kdlae_t_handle* h) { return h ? h->ps.lay.total : -1; }
 
 int kdlae_t_set_param(kdlae_t_handle* h, const char* name, const float* host_data, int64_t numel) {
   if (!h || !name || !host_data) return fail(KDLAE_ESTATE, "null argument");
@@ -968,7 +900,7 @@ static int build_program(kdlae_t_handle* h) {
   if (h->built) return KDLAE_OK;
   const kdlae_t_config& c = h->cfg;
   Packer pk{h};
-  pk.prog.nsrc = h->ps.total;
+  pk.prog.nsrc = h->ps.lay.total;
   h->zeros = pk.prog.add(std::vector<PEx>(64));
   const int d = c.dim;
   const int* nb = c.num_blocks;
@@ -1030,9 +962,9 @@ int kdlae_t_prepare(kdlae_t_handle* h) {
 
 int kdlae_t_pack_device(kdlae_t_handle* h, const float* params, int64_t numel, void* stream) {
   if (!h) return fail(KDLAE_ESTATE, "null handle");
-  if (numel != h->ps.total)
+  if (numel != h->ps.lay.total)
     return fail(KDLAE_EPARAM, "flat parameter vector has " + std::to_string(numel) + " floats, expected " +
-                                  std::to_string(h->ps.total));
+                                  std::to_string(h->ps.lay.total));
   int rc = build_program(h);
   if (rc) return rc;
   DeviceGuard g(h->device);

@@ -21,10 +21,14 @@
 #include <vector>
 
 #include "../../include/kdlae.h"
+#include "param_layout.h"
 #include "runtime.h"
 #include "train_kernels.h"
 
+using kdlae::al16;
 using kdlae::fail;
+using kdlae::hid_of;
+using kdlae::ld4;
 namespace tr = kdlae::train;
 
 namespace {
@@ -58,9 +62,7 @@ struct Saved {
 struct kdlae_tt_handle {
   kdlae_t_config cfg{};
   int device = 0;
-  std::vector<std::pair<std::string, int64_t>> keys;
-  std::unordered_map<std::string, int64_t> off;
-  int64_t total = 0;
+  kdlae::ParamLayout lay{4};  // state_dict order, every key 16-byte aligned
   Saved sv;
   int ws_B = -1, ws_H = -1, ws_W = -1;  // last kdlae_tt_workspace_bytes query (its dry run is cached)
   int64_t ws_bytes = -1;
@@ -100,71 +102,6 @@ struct kdlae_tt_handle {
 };
 
 namespace {
-
-int hid_of(const kdlae_t_config& c, int dim) { return (int)((double)dim * c.ffn_expansion_factor); }
-
-// state_dict order of KDLAE_teacher (KDLAE_model.py:220-268; TransformerBlock :150-157)
-void build_keys(kdlae_tt_handle* h) {
-  const kdlae_t_config& c = h->cfg;
-  // every key starts on a 16-byte boundary (pad floats stay zero), so the weight operands of the
-  // training GEMMs (temperature [heads] and ffn.dwconv [2 hid * 9] break 4-float alignment
-  // otherwise) qualify for the vectorised kernel
-  auto add = [&](const std::string& k, int64_t n) {
-    h->off[k] = h->total;
-    h->keys.emplace_back(k, n);
-    h->total += (n + 3) & ~int64_t(3);
-  };
-  auto conv = [&](const std::string& n, int co, int ci, int k, bool b) {
-    add(n + ".weight", (int64_t)co * ci * k * k);
-    if (b) add(n + ".bias", co);
-  };
-  auto block = [&](const std::string& p, int dim, int heads) {
-    const int hid = hid_of(c, dim);
-    add(p + ".norm1.body.weight", dim);
-    if (!c.layernorm_biasfree) add(p + ".norm1.body.bias", dim);
-    add(p + ".attn.temperature", heads);
-    conv(p + ".attn.qkv", 3 * dim, dim, 1, c.bias);
-    conv(p + ".attn.qkv_dwconv", 3 * dim, 1, 3, c.bias);
-    conv(p + ".attn.project_out", dim, dim, 1, c.bias);
-    add(p + ".norm2.body.weight", dim);
-    if (!c.layernorm_biasfree) add(p + ".norm2.body.bias", dim);
-    conv(p + ".ffn.project_in", 2 * hid, dim, 1, c.bias);
-    conv(p + ".ffn.dwconv", 2 * hid, 1, 3, c.bias);
-    conv(p + ".ffn.project_out", dim, hid, 1, c.bias);
-  };
-  auto stage = [&](const std::string& n, int cnt, int dim, int heads) {
-    for (int i = 0; i < cnt; ++i) block(n + "." + std::to_string(i), dim, heads);
-  };
-  const int d = c.dim, *nb = c.num_blocks, *hd = c.heads, nr = c.num_refinement_blocks;
-  conv("patch_embed.proj", d, c.inp_channels, 3, false);
-  stage("encoder_level1", nb[0], d, hd[0]);
-  conv("down1_2.body.0", d / 2, d, 3, false);
-  stage("encoder_level2", nb[1], 2 * d, hd[1]);
-  conv("down2_3.body.0", d, 2 * d, 3, false);
-  stage("encoder_level3", nb[2], 4 * d, hd[2]);
-  conv("down3_4.body.0", 2 * d, 4 * d, 3, false);
-  stage("latent", nb[3], 8 * d, hd[3]);
-  conv("up4_3.body.0", 16 * d, 8 * d, 3, false);
-  conv("reduce_chan_level3", 4 * d, 8 * d, 1, c.bias);
-  stage("decoder_level3", nb[2], 4 * d, hd[2]);
-  conv("up3_2.body.0", 8 * d, 4 * d, 3, false);
-  conv("reduce_chan_level2", 2 * d, 4 * d, 1, c.bias);
-  stage("decoder_level2", nb[1], 2 * d, hd[1]);
-  conv("up2_1.body.0", 4 * d, 2 * d, 3, false);
-  stage("decoder_level1", nb[0], 2 * d, hd[0]);
-  stage("refinement", nr, 2 * d, hd[0]);
-  conv("output", c.out_channels, 2 * d, 3, c.bias);
-  conv("output_param", 2 * d, c.out_channels + 1, 3, c.bias);
-  stage("refinement_out", nr, 2 * d, hd[0]);
-  conv("output2", c.out_channels, 2 * d, 3, c.bias);
-  if (c.static_train) {
-    const int hc = 2 * d;
-    conv("cen", hc, c.out_channels, 3, c.bias);
-    conv("upen.body.0", 2 * hc, hc, 3, false);
-    stage("enhance", nr, hc / 2, hd[0]);
-    conv("outputen", c.out_channels, hc / 2, 3, c.bias);
-  }
-}
 
 int validate(const kdlae_t_config& c) {
   if (c.dual_pixel_task)
@@ -239,18 +176,18 @@ struct Ctx {
     return p;
   }
   const float* W(const std::string& k) const {
-    auto it = h->off.find(k);
-    return it == h->off.end() ? nullptr : th + it->second;
+    const int64_t o = h->lay.find(k);
+    return o < 0 ? nullptr : th + o;
   }
   float* G(const std::string& k) const {
-    auto it = h->off.find(k);
-    if (it == h->off.end()) return nullptr;
+    const int64_t o = h->lay.find(k);
+    if (o < 0) return nullptr;
     if (touch) {
-      auto t = touch->find(it->second);
-      if (t == touch->end()) touch->emplace(it->second, std::make_pair(cur_mark, cur_mark));
+      auto t = touch->find(o);
+      if (t == touch->end()) touch->emplace(o, std::make_pair(cur_mark, cur_mark));
       else t->second.second = cur_mark;
     }
-    return gr + it->second;
+    return gr + o;
   }
 };
 
@@ -375,14 +312,6 @@ void trace_end(Ctx& c, hipEvent_t a, const char* what) {
       if (e_ != hipSuccess) return fail(KDLAE_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
     }                                                                                                \
   } while (0)
-#define TRY(x)                  \
-  do {                          \
-    int r_ = (x);               \
-    if (r_ != KDLAE_OK) return r_; \
-  } while (0)
-
-inline int ld4(int n) { return (n + 3) / 4 * 4; }
-
 // the current stream's queued reductions, on that stream (its partials were written there, and its
 // later writes to the same `red` buffer follow the flush in stream order)
 int flush_reduce(Ctx& c) {
@@ -526,8 +455,6 @@ int conv1_bwd(Ctx& c, const std::string& n, V x, V dy, int Cin, int Cout, long l
   return KDLAE_OK;
 }
 
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // A 3x3 conv with a narrow side (<= 4 channels: the image heads and the 3- / 4-channel inputs) is a
 // 64-wide GEMM tile that is mostly padding; those run on the inference path's small-channel kernels
 // (conv_small.hip): narrow input -> the MFMA small-input kernel (K = 9 Cin <= 36), narrow output ->
@@ -592,10 +519,7 @@ int pack_w3(Ctx& c, tr::TGemm& g, int N) {
   if (kdlae::debug_flag("train_w3_raw") || N % 4) return KDLAE_OK;
   float* wp = c.alloc((size_t)9 * g.Cg * N);
   LAUNCH(tr::launch_pack_w3(g.B, g.Cg, N, g.bmode, wp, c.s));
-  g.B = wp;
-  g.bmode = 0;
-  g.sbk = N;
-  g.sbn = 1;
+  tr::use_packed_w3(g, wp, N);
   return KDLAE_OK;
 }
 
@@ -1202,7 +1126,7 @@ int kdlae_tt_create(const kdlae_t_config* cfg, int device, kdlae_tt_handle** out
   auto* h = new kdlae_tt_handle();
   h->cfg = *cfg;
   h->device = device;
-  build_keys(h);
+  kdlae::teacher_keys(h->cfg, h->lay);
   *out = h;
   return KDLAE_OK;
 }
@@ -1212,17 +1136,14 @@ int kdlae_tt_destroy(kdlae_tt_handle* h) {
   return KDLAE_OK;
 }
 
-int kdlae_tt_num_params(const kdlae_tt_handle* h) { return h ? (int)h->keys.size() : 0; }
+int kdlae_tt_num_params(const kdlae_tt_handle* h) { return h ? h->lay.size() : 0; }
 
 int kdlae_tt_param_info(const kdlae_tt_handle* h, int index, const char** name, int64_t* numel, int64_t* offset) {
-  if (!h || index < 0 || index >= (int)h->keys.size()) return fail(KDLAE_EPARAM, "param index out of range");
-  if (name) *name = h->keys[index].first.c_str();
-  if (numel) *numel = h->keys[index].second;
-  if (offset) *offset = h->off.at(h->keys[index].first);
-  return KDLAE_OK;
+  if (!h) return fail(KDLAE_EPARAM, "param index out of range");
+  return h->lay.info(index, name, numel, offset);
 }
 
-int64_t kdlae_tt_num_floats(const kdlae_tt_handle* h) { return h ? h->total : -1; }
+int64_t kdlae_tt_num_floats(const kdlae_tt_handle* h) { return h ? h->lay.total : -1; }
 
 static int check_shape(int B, int H, int W) {
   if (B <= 0 || H <= 0 || W <= 0) return fail(KDLAE_EINVAL_SHAPE, "B, H, W must be positive");
@@ -1301,7 +1222,7 @@ int kdlae_tt_backward(kdlae_tt_handle* h, const float* theta, const float* dhq, 
   if (kdlae::debug_flag("train_trace")) c.trace = &h->trace;
   int rc = use_side_stream(c, h);
   if (rc) return rc;
-  hipError_t e = hipMemsetAsync(grad, 0, (size_t)h->total * sizeof(float), (hipStream_t)stream);
+  hipError_t e = hipMemsetAsync(grad, 0, (size_t)h->lay.total * sizeof(float), (hipStream_t)stream);
   if (e != hipSuccess) return fail(KDLAE_EHIP, hipGetErrorString(e));
   rc = net_bwd(c, dhq, dsr, has_dsr);
   if (rc == KDLAE_OK) rc = flush_all(c);
@@ -1338,11 +1259,11 @@ int kdlae_tt_backward_marked(kdlae_tt_handle* h, const float* theta, const float
     h->mark_slot.assign(nmarks, -1);
     h->mark_lo.clear();
     h->mk_touch = touch;
-    std::vector<int64_t> first_lo(nmarks, h->total);  // lowest offset first written at or before mark m
+    std::vector<int64_t> first_lo(nmarks, h->lay.total);  // lowest offset first written at or before mark m
     for (const auto& kv : touch) {
       for (int m = kv.second.first; m < nmarks && kv.first < first_lo[m]; ++m) first_lo[m] = kv.first;
     }
-    int64_t prev_lo = h->total;
+    int64_t prev_lo = h->lay.total;
     for (int m = 0; m < nmarks; ++m) {
       const int64_t lo = first_lo[m];
       if (lo >= prev_lo) continue;
@@ -1379,7 +1300,7 @@ int kdlae_tt_backward_marked(kdlae_tt_handle* h, const float* theta, const float
   if (kdlae::debug_flag("train_trace")) c.trace = &h->trace;
   int rc = use_side_stream(c, h);
   if (rc) return rc;
-  hipError_t e = hipMemsetAsync(grad, 0, (size_t)h->total * sizeof(float), (hipStream_t)stream);
+  hipError_t e = hipMemsetAsync(grad, 0, (size_t)h->lay.total * sizeof(float), (hipStream_t)stream);
   if (e != hipSuccess) return fail(KDLAE_EHIP, hipGetErrorString(e));
   rc = net_bwd(c, dhq, dsr, has_dsr);
   if (rc == KDLAE_OK) rc = flush_all(c);

@@ -120,48 +120,6 @@ constexpr auto KDLAE_KPEN_1X1 = 0.02;
 }
 
 
-int ParamStore::set(const char* name, const float* data, int64_t numel) {
-  auto it = index.find(name);
-  if (it == index.end()) return fail(KDLAE_EPARAM, std::string("unexpected key in state_dict: ") + name);
-  if (keys[it->second].second != numel)
-    return fail(KDLAE_EPARAM, std::string("size mismatch for ") + name + ": expected " +
-                                  std::to_string(keys[it->second].second) + " got " + std::to_string(numel));
-  staged[name].assign(data, data + numel);
-  return KDLAE_OK;
-}
-
-int ParamStore::info(int i, const char** name, int64_t* numel) const {
-  if (i < 0 || i >= (int)keys.size()) return fail(KDLAE_EPARAM, "param index out of range");
-  if (name) *name = keys[i].first.c_str();
-  if (numel) *numel = keys[i].second;
-  return KDLAE_OK;
-}
-
-int ParamStore::check_complete() const {
-  for (auto& kv : keys)
-    if (!staged.count(kv.first)) return fail(KDLAE_EPARAM, "missing state_dict entry: " + kv.first);
-  return KDLAE_OK;
-}
-
-
-int32_t ParamStore::base(const std::string& k, int* err) const {
-  auto it = index.find(k);
-  if (it == index.end()) {
-    if (err && *err == KDLAE_OK) *err = fail(KDLAE_EPARAM, "missing state_dict entry: " + k);
-    return -1;
-  }
-  return (int32_t)offset[it->second];
-}
-
-std::vector<float> ParamStore::flat() const {
-  std::vector<float> v((size_t)total, 0.f);
-  for (size_t i = 0; i < keys.size(); ++i) {
-    auto it = staged.find(keys[i].first);
-    if (it != staged.end()) std::copy(it->second.begin(), it->second.end(), v.begin() + offset[i]);
-  }
-  return v;
-}
-
 int run_gemm(const GemmCall& c, hipStream_t s) {
   const Gemm& g = *c.g;
   const long long HW = (long long)c.F * c.H * c.Wd;

@@ -29,7 +29,16 @@ bool debug_flag(const char* name);
     if (e_ != hipSuccess) return ::kdlae::fail(KDLAE_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
   } while (0)
 
+// propagate a KDLAE_* status
+#define TRY(x)                     \
+  do {                             \
+    int rc_ = (x);                 \
+    if (rc_ != KDLAE_OK) return rc_; \
+  } while (0)
+
 inline int ru16(int x) { return (x + 15) / 16 * 16; }
+inline int ld4(int n) { return (n + 3) / 4 * 4; }
+inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 inline long long ceil_div(long long a, long long b) { return (a + b - 1) / b; }
 constexpr size_t kNone = (size_t)-1;
 
@@ -120,26 +129,6 @@ std::vector<PEx> pack_fragments(int ntiles, int kgroups, F Wf) {
   return v;
 }
 
-// expected state_dict keys (flat offsets in key order) + host copies staged through *_set_param
-struct ParamStore {
-  std::vector<std::pair<std::string, int64_t>> keys;
-  std::vector<int64_t> offset;
-  int64_t total = 0;
-  std::unordered_map<std::string, int> index;
-  std::unordered_map<std::string, std::vector<float>> staged;
-  void add(const std::string& k, int64_t n) {
-    index[k] = (int)keys.size();
-    keys.emplace_back(k, n);
-    offset.push_back(total);
-    total += n;
-  }
-  int set(const char* name, const float* data, int64_t numel);
-  int info(int i, const char** name, int64_t* numel) const;
-  int check_complete() const;
-  int32_t base(const std::string& k, int* err) const;  // flat offset of a key (-1 + err if unknown)
-  std::vector<float> flat() const;                       // staged entries in key order
-};
-
 // Device side of a handle's weights: the packed arena plus the pack program that fills it.
 struct DeviceWeights {
   float* dev = nullptr;       // packed arena
@@ -178,6 +167,16 @@ struct DeviceGuard {
   }
 };
 
+// Base of the handles' workspace plans: offsets in bytes, every buffer 256-byte aligned.
+struct WsPlan {
+  size_t total = 0;
+  size_t take(long long floats) {
+    const size_t off = total;
+    total += ((size_t)floats * 4 + 255) / 256 * 256;
+    return off;
+  }
+};
+
 struct View {
   float* p;
   int ld;
@@ -207,5 +206,7 @@ int run_gemm(const GemmCall& c, hipStream_t s);
 // Compute units of the current device (256 on MI355X) and the tail-aware GEMM grid split.
 int device_cu_count();  // of the current device
 int gemm_tiles_per_block(int total_tiles, int gy, bool resident, int wpe);
+// Partial Gram slots per (image, head) of the KDLAE-T attention at image size H x W (kdlae_t.cpp)
+int nslots_for(int H, int W);
 
 }  // namespace kdlae

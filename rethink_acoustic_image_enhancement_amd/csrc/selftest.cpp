@@ -181,13 +181,7 @@ extern "C" int kdlae_debug_gram(const kdlae_debug_gram_desc* d, void* stream) {
   p.Bn = d->Bn;
   p.H = d->H;
   p.W = d->W;
-  // the engine's slot count (kdlae_t.cpp nslots_for)
-  if (d->W % 16 == 0) {
-    p.nslots = (d->W / 16) * std::max(1, std::min(8, (d->H + 31) / 32));
-  } else {
-    const int steps = (d->H * d->W + 63) / 64;
-    p.nslots = std::max(1, std::min(64, (steps + 15) / 16));
-  }
+  p.nslots = kdlae::nslots_for(d->H, d->W);  // the engine's slot count
   const int CT = p.Ch / 16;
   p.slot_floats = CT * CT * 256 + 2 * p.Ch;
   p.zeros = d->route == 0 ? d->zeros : nullptr;
@@ -289,7 +283,7 @@ extern "C" int kdlae_debug_bn(const kdlae_debug_bn_desc* d, void* stream) {
 namespace {
 
 constexpr long long kMaxIdx = 1LL << 31;  // the kernels' 32-bit index math; far above any self-test shape
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+using kdlae::al16;
 // a [pixels][ld] view of `width` used columns
 inline bool view_ok(const void* p, int ld, int width, long long pixels) {
   return p && width >= 1 && ld >= width && pixels >= 1 && pixels * ld < kMaxIdx;

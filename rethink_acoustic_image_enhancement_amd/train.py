@@ -178,40 +178,33 @@ def _reflect_pad(t, multiple):
     return t
 
 
-class TrainEngine:
-    """``kdlae_tt_*`` handle for one KDLAE_teacher config on one device."""
+class _FlatEngine:
+    """A ``{prefix}_*`` training handle for one model config on one device: the flat parameter layout
+    (``keys``: ``(name, numel, offset)`` in ``named_parameters()`` order, every key 16-byte aligned; ``numel``:
+    floats of the flat buffer) and the workspace ``ws``, grown on demand."""
 
-    def __init__(self, model, device: torch.device):
+    def __init__(self, prefix, model, device: torch.device, what):
         L = _lib.lib()
-        self.device = device
+        self._L, self._prefix, self.device = L, prefix, device
         h = ctypes.c_void_p()
         idx = device.index if device.index is not None else torch.cuda.current_device()
-        _lib.check(L.kdlae_tt_create(ctypes.byref(model._c_config()), idx, ctypes.byref(h)), "kdlae_tt_create")
+        _lib.check(self._fn("create")(ctypes.byref(model._c_config()), idx, ctypes.byref(h)), prefix + "_create")
         self.handle = h
-        self._L = L
+        self._dtor = self._fn("destroy")
         self.keys = []
-        for i in range(L.kdlae_tt_num_params(h)):
+        for i in range(self._fn("num_params")(h)):
             name, numel, off = ctypes.c_char_p(), ctypes.c_int64(), ctypes.c_int64()
-            _lib.check(L.kdlae_tt_param_info(h, i, ctypes.byref(name), ctypes.byref(numel), ctypes.byref(off)),
-                       "kdlae_tt_param_info")
+            _lib.check(self._fn("param_info")(h, i, ctypes.byref(name), ctypes.byref(numel), ctypes.byref(off)),
+                       prefix + "_param_info")
             self.keys.append((name.value.decode(), int(numel.value), int(off.value)))
-        self.numel = int(L.kdlae_tt_num_floats(h))
-        names = [k for k, _, _ in self.keys]
-        sd_names = [k for k, _ in model.named_parameters()]
-        if names != sd_names:
-            raise RuntimeError("KDLAE_teacher parameters do not match the training handle's state_dict layout")
-        cfg = model._cfg
-        self.static_train = cfg["static"] == "train"
-        self.params_cat = cfg["params"] == "cat"
-        self.out_channels = cfg["out_channels"]
-        # parameters the reference forward never touches (KDLAE_model.py:315-319 when params != 'cat'):
-        # autograd leaves their .grad None and torch.optim skips them
-        unused = ("output_param.", "refinement_out.") if not self.params_cat else ()
-        self.used = [not k.startswith(unused) for k in names]
+        self.numel = int(self._fn("num_floats")(h))
+        if [k for k, _, _ in self.keys] != [k for k, _ in model.named_parameters()]:
+            raise RuntimeError(f"{what} parameters do not match the training handle's state_dict layout")
         self.ws = None
-        self.ws_shape = None
         self.generation = 0
-        self._dtor = L.kdlae_tt_destroy
+
+    def _fn(self, name):
+        return getattr(self._L, f"{self._prefix}_{name}")
 
     def __del__(self):
         try:
@@ -221,17 +214,8 @@ class TrainEngine:
             pass
 
     def used_ranges(self):
-        """[begin, end) float ranges of the flat buffer that receive gradients (merged)."""
-        out = []
-        for (k, n, off), u in zip(self.keys, self.used):
-            if not u:
-                continue
-            end = off + ((n + 3) & ~3)  # keys are 16-byte aligned; the zero pad floats ride along
-            if out and out[-1][1] == off:
-                out[-1][1] = end
-            else:
-                out.append([off, end])
-        return out
+        """[begin, end) float ranges of the flat buffer that receive gradients: all of it."""
+        return [[0, self.numel]]
 
     def flatten(self, tensors) -> torch.Tensor:
         """Parameters -> the handle's flat layout (state_dict order, each key 16-byte aligned, pads zero)."""
@@ -245,14 +229,42 @@ class TrainEngine:
         """The flat layout without its pad floats: torch.cat of the keys in state_dict order."""
         return torch.cat([flat[off:off + n] for _, n, off in self.keys])
 
-    def _workspace(self, B, H, W):
-        nbytes = int(self._L.kdlae_tt_workspace_bytes(self.handle, B, H, W))
+    def _workspace(self, *shape):
+        nbytes = int(self._fn("workspace_bytes")(self.handle, *shape))
         if nbytes < 0:
-            _lib.check(1, "kdlae_tt_workspace_bytes")
+            _lib.check(1, self._prefix + "_workspace_bytes")
         if self.ws is None or self.ws.numel() < nbytes:
             self.ws = None
             self.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         return self.ws
+
+
+class TrainEngine(_FlatEngine):
+    """``kdlae_tt_*`` handle for one KDLAE_teacher config on one device."""
+
+    def __init__(self, model, device: torch.device):
+        super().__init__("kdlae_tt", model, device, "KDLAE_teacher")
+        cfg = model._cfg
+        self.static_train = cfg["static"] == "train"
+        self.params_cat = cfg["params"] == "cat"
+        self.out_channels = cfg["out_channels"]
+        # parameters the reference forward never touches (KDLAE_model.py:315-319 when params != 'cat'):
+        # autograd leaves their .grad None and torch.optim skips them
+        unused = ("output_param.", "refinement_out.") if not self.params_cat else ()
+        self.used = [not k.startswith(unused) for k, _, _ in self.keys]
+
+    def used_ranges(self):
+        """[begin, end) float ranges of the flat buffer that receive gradients (merged)."""
+        out = []
+        for (k, n, off), u in zip(self.keys, self.used):
+            if not u:
+                continue
+            end = off + ((n + 3) & ~3)  # keys are 16-byte aligned; the zero pad floats ride along
+            if out and out[-1][1] == off:
+                out[-1][1] = end
+            else:
+                out.append([off, end])
+        return out
 
     def forward(self, theta, img, rate):
         """KDLAE_teacher.forward (KDLAE_model.py:270-336) with activations kept for ``backward``."""
@@ -382,42 +394,11 @@ class L1LossSr(torch.nn.Module):
 
 
 # ------------------------------------------------------------------ KDLAE-S (KDLAES.yml)
-class StudentTrainEngine:
+class StudentTrainEngine(_FlatEngine):
     """``kdlae_st_*`` handle for one KDLAE_student config on one device (KDLAE_model.py:340-431)."""
 
     def __init__(self, model, device: torch.device):
-        L = _lib.lib()
-        self.device = device
-        h = ctypes.c_void_p()
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        _lib.check(L.kdlae_st_create(ctypes.byref(model._c_config()), idx, ctypes.byref(h)), "kdlae_st_create")
-        self.handle = h
-        self._L = L
-        self.keys = []
-        for i in range(L.kdlae_st_num_params(h)):
-            name, numel, off = ctypes.c_char_p(), ctypes.c_int64(), ctypes.c_int64()
-            _lib.check(L.kdlae_st_param_info(h, i, ctypes.byref(name), ctypes.byref(numel), ctypes.byref(off)),
-                       "kdlae_st_param_info")
-            self.keys.append((name.value.decode(), int(numel.value), int(off.value)))
-        self.numel = int(L.kdlae_st_num_floats(h))
-        if [k for k, _, _ in self.keys] != [k for k, _ in model.named_parameters()]:
-            raise RuntimeError("KDLAE_student parameters do not match the training handle's state_dict layout")
-        self.ws = None
-        self.generation = 0
-        self._dtor = L.kdlae_st_destroy
-
-    def __del__(self):
-        try:
-            if self.handle:
-                self._dtor(self.handle)
-        except Exception:
-            pass
-
-    def used_ranges(self):
-        return [[0, self.numel]]
-
-    flatten = TrainEngine.flatten
-    packed = TrainEngine.packed
+        super().__init__("kdlae_st", model, device, "KDLAE_student")
 
     def forward(self, theta, x):
         """KDLAE_student.forward with activations kept for ``backward``: x [B, F, H, W] -> [B, F, H, W]."""
@@ -425,12 +406,7 @@ class StudentTrainEngine:
             raise RuntimeError("KDLAE training runs on ROCm devices only; there is no CPU fallback")
         x = x.detach().to(torch.float32).contiguous()
         B, F, H, W = x.shape
-        nbytes = int(self._L.kdlae_st_workspace_bytes(self.handle, B, F, H, W))
-        if nbytes < 0:
-            _lib.check(1, "kdlae_st_workspace_bytes")
-        if self.ws is None or self.ws.numel() < nbytes:
-            self.ws = None
-            self.ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        self._workspace(B, F, H, W)
         out = torch.empty_like(x)
         self._x = x  # the residual input must outlive the backward
         rc = self._L.kdlae_st_forward(self.handle, _vp(theta), _vp(x), B, F, H, W, _vp(out), _vp(self.ws),
@@ -642,30 +618,14 @@ def asdqe_dropout_masks(B, device, generator=None):
     return m1, m2
 
 
-class AsdqeTrainEngine:
+class AsdqeTrainEngine(_FlatEngine):
     """``asdqe_train_*`` handle for one DenoiseRatePredictor config on one device (ASDQE_model.py:123-171
     in train mode: batch-statistics BatchNorm with the running update, Dropout by explicit masks)."""
 
     def __init__(self, model, device: torch.device):
-        L = _lib.lib()
-        self.device = device
-        h = ctypes.c_void_p()
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        _lib.check(L.asdqe_train_create(ctypes.byref(model._c_config()), idx, ctypes.byref(h)), "asdqe_train_create")
-        self.handle = h
-        self._L = L
-        self._dtor = L.asdqe_train_destroy
-        self.keys = []
-        for i in range(L.asdqe_train_num_params(h)):
-            name, numel, off = ctypes.c_char_p(), ctypes.c_int64(), ctypes.c_int64()
-            _lib.check(L.asdqe_train_param_info(h, i, ctypes.byref(name), ctypes.byref(numel), ctypes.byref(off)),
-                       "asdqe_train_param_info")
-            self.keys.append((name.value.decode(), int(numel.value), int(off.value)))
-        self.numel = int(L.asdqe_train_num_floats(h))
-        self.num_stats = int(L.asdqe_train_num_stat_floats(h))
+        super().__init__("asdqe_train", model, device, "DenoiseRatePredictor")
+        self.num_stats = int(self._L.asdqe_train_num_stat_floats(self.handle))
         self.in_channels = int(model._cfg["in_channels"])
-        if [k for k, _, _ in self.keys] != [k for k, _ in model.named_parameters()]:
-            raise RuntimeError("DenoiseRatePredictor parameters do not match the training handle's layout")
         # per BatchNorm2d, in state_dict order: [running_mean | running_var] at this offset
         self.stat_slots, off = [], 0
         for bn in _bn_modules(model):
@@ -673,21 +633,6 @@ class AsdqeTrainEngine:
             off += 2 * bn.num_features
         if off != self.num_stats:
             raise RuntimeError("DenoiseRatePredictor BatchNorm buffers do not match the training handle's layout")
-        self.ws = None
-        self.generation = 0
-
-    def __del__(self):
-        try:
-            if self.handle:
-                self._dtor(self.handle)
-        except Exception:
-            pass
-
-    def used_ranges(self):
-        return [[0, self.numel]]
-
-    flatten = TrainEngine.flatten
-    packed = TrainEngine.packed
 
     def flatten_stats(self, model) -> torch.Tensor:
         bns = _bn_modules(model)
@@ -712,12 +657,7 @@ class AsdqeTrainEngine:
                 raise RuntimeError(f"dropout mask must be a [{B}, {n}] tensor on {lq.device}")
         mask1 = mask1.detach().to(torch.float32).contiguous() if mask1 is not None else None
         mask2 = mask2.detach().to(torch.float32).contiguous() if mask2 is not None else None
-        nbytes = int(self._L.asdqe_train_workspace_bytes(self.handle, B, H, W))
-        if nbytes < 0:
-            _lib.check(1, "asdqe_train_workspace_bytes")
-        if self.ws is None or self.ws.numel() < nbytes:
-            self.ws = None
-            self.ws = torch.empty(nbytes, dtype=torch.uint8, device=lq.device)
+        self._workspace(B, H, W)
         score = torch.empty((B, 1), dtype=torch.float32, device=lq.device)
         rc = self._L.asdqe_train_forward(self.handle, _vp(theta), _vp(stats), _vp(lq), _vp(gt), B, H, W, _vp(mask1),
                                          _vp(mask2), _vp(score), _vp(self.ws), self.ws.numel(), _stream(lq.device))
