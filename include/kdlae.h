@@ -414,6 +414,32 @@ int64_t kdlae_metric_scratch_bytes(void);
 int kdlae_metric_psnr(const float* pred, const float* gt, int B, int C, int Hs, int Ws, int Hg, int Wg, int h, int w,
                       int crop_border, int mode, double* out, void* scratch, void* stream);
 
+/* ---- SSIM (ssim.hip).  The other metric of the reference's val.metrics block, over the same geometry and
+ * with the same `mode` as the PSNR entry above: the top-left h x w window of both stored tensors minus
+ * crop_border on the four sides; mode 1 quantises both operands as tensor2img does.  Five windowed means
+ * (mu1, mu2, E[x^2], E[y^2], E[xy]; the 11 taps g[i] = exp(-(i - 5)^2 / (2 * 1.5^2)) / sum on each axis) and the
+ * map (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s1^2 + s2^2 + C2)), C1 = (0.01 L)^2, C2 = (0.03 L)^2.
+ *   variant 0: calculate_ssim -> _ssim_3d (Train/basicsr/metrics/psnr_ssim.py:146-197,240-318): the 11^3 Conv3d
+ *              over the (H, W, C) volume with replicate padding, i.e. filter indices clamped to the edge of the
+ *              compared window on H and W (never to stored pixels beyond it) and a C x C mix along the channels
+ *              (the squares and the product are formed before the mix).  h * w * C map entries; L = 1 when
+ *              max(pred) <= 1, else 255 (:307).  1 <= C <= 4.
+ *   variant 1: Train/utils.py:31-78 (= _ssim, psnr_ssim.py:73-114): per channel, valid positions only, so
+ *              (h' - 10)(w' - 10) entries per channel of the cropped h' x w' window; L = 255.  h', w' >= 11.
+ * out [B][4] (device, fp64): out[b][0] = sum of the map with the L = 1 constants (variant 1: 0), out[b][1] =
+ * the sum with the L = 255 constants, out[b][2] = max of pred over the region (after the quantisation in
+ * mode 1), out[b][3] = the number of map entries.  SSIM = out[b][max <= 1 ? 0 : 1] / out[b][3] (variant 0),
+ * out[b][1] / out[b][3] (variant 1): both sums come from one pass, so nothing synchronises and the result
+ * stays on the device.  Taps, moments, map and sums are fp64 (E[x^2] - mu^2 against C2 = 9e-4 L^2 is where fp32
+ * loses its digits); fixed two-stage order without atomics: equal inputs give equal bits, and equal
+ * operands give exactly 1.  Nothing outside the compared region is read.  Errors are found before any launch:
+ * window / crop_border as above, variant 1 under 11 pixels or variant 0 with C > 4: KDLAE_EINVAL_SHAPE.
+ * scratch: device buffer of the size the first function below returns, in bytes (8-byte aligned). */
+int64_t kdlae_metric_ssim_scratch_bytes(void);
+int kdlae_metric_ssim(const float* pred, const float* gt, int B, int C, int Hs, int Ws, int Hg, int Wg,
+                      int h, int w, int crop_border, int mode, int variant,
+                      double* out, void* scratch, void* stream);
+
 /* ---- Kernel self-test entry points (not part of the drop-in boundary; nothing here is on a forward
  * or training path).  tests/test_kernel_variants*_gpu.py: kdlae_debug_tgemm, kdlae_debug_gemm,
  * kdlae_debug_gram, kdlae_debug_ln, kdlae_debug_small_in, kdlae_debug_bn;

@@ -52,6 +52,7 @@ EXPORTS = (
     "asdqe_train_backward", "kdlae_train_mse",
     "kdlae_debug_bn",
     "kdlae_metric_scratch_bytes", "kdlae_metric_psnr",
+    "kdlae_metric_ssim_scratch_bytes", "kdlae_metric_ssim",
     "kdlae_debug_train", "kdlae_debug_train_blocks", "kdlae_debug_train_s",
     "kdlae_debug_infer",
 )
@@ -257,6 +258,10 @@ def lib() -> ctypes.CDLL:
     L.kdlae_metric_scratch_bytes.restype = c_int64
     L.kdlae_metric_psnr.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                     c_int, c_int, c_void_p, c_void_p, c_void_p]
+    L.kdlae_metric_ssim_scratch_bytes.argtypes = []
+    L.kdlae_metric_ssim_scratch_bytes.restype = c_int64
+    L.kdlae_metric_ssim.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                    c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
     L.kdlae_debug_tgemm.argtypes = [c_void_p, c_void_p]
     for f in ("kdlae_debug_gemm", "kdlae_debug_gram", "kdlae_debug_ln", "kdlae_debug_small_in",
               "kdlae_debug_train", "kdlae_debug_train_s", "kdlae_debug_infer"):

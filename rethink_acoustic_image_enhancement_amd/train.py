@@ -178,6 +178,18 @@ def _reflect_pad(t, multiple):
     return t
 
 
+def _val_metrics(metrics):
+    """``validate(metrics=...)``: the names of the reference's val.metrics block this build has
+    (calculate_psnr, calculate_ssim), checked -> (want PSNR, want SSIM)."""
+    names = (metrics,) if isinstance(metrics, str) else tuple(metrics)
+    for m in names:
+        if m not in ("psnr", "ssim"):
+            raise ValueError(f"validate: unknown metric {m!r} (expected 'psnr' and / or 'ssim')")
+    if not names:
+        raise ValueError("validate: no metrics")
+    return "psnr" in names, "ssim" in names
+
+
 class _FlatEngine:
     """A ``{prefix}_*`` training handle for one model config on one device: the flat parameter layout
     (``keys``: ``(name, numel, offset)`` in ``named_parameters()`` order, every key 16-byte aligned; ``numel``:
@@ -582,26 +594,37 @@ class KDLAESTrainer(_TrainingState):
         return self._opt_scratch[2048]
 
     @torch.no_grad()
-    def validate(self, batches, window_size=8, crop_border=0, use_image=False):
+    def validate(self, batches, window_size=8, crop_border=0, use_image=False, metrics=("psnr",)):
         """ImageCleanModel.nondist_validation (image_restoration_model.py:264-348) for ``(lq, gt)`` pairs of
         [B, F, H, W] tensors: reflect-pad to the multiple the student needs (2^levels, and ``window_size``),
         the inference engine, PSNR of the top-left H x W window against ``gt``.  Returns ``{'psnr': mean}``
-        over all images.  The trainer's state is untouched."""
-        from .metrics import psnr_batch
+        over all images; with ``"ssim"`` in ``metrics`` also ``{'ssim': mean}`` (``calculate_ssim`` over the
+        same window, 1 <= F <= 4 frames).  The trainer's state is untouched."""
+        from .metrics import psnr_batch, ssim_batch
+        want_psnr, want_ssim = _val_metrics(metrics)
         need = 1 << self.model.num_levels
         mult = math.lcm(need, int(window_size)) if window_size else need
         flat = _inference_flat(self, self.theta)
-        vals = []
+        vals, ssims, seen = [], [], False
         for lq, gt in batches:
             if lq.device.type != "cuda":
                 raise RuntimeError("KDLAE validation runs on ROCm devices only; there is no CPU fallback")
             h, w = lq.shape[-2:]
             out = self.model._forward_eager(_reflect_pad(lq.to(torch.float32), mult), flat=flat)
             self.val_output = out[..., :h, :w]  # the last item's cropped output (pad_test's self.output)
-            vals.append(psnr_batch(out, gt.to(out.device), (h, w), crop_border, use_image))
-        if not vals:
+            seen = True
+            if want_psnr:
+                vals.append(psnr_batch(out, gt.to(out.device), (h, w), crop_border, use_image))
+            if want_ssim:
+                ssims.append(ssim_batch(out, gt.to(out.device), (h, w), crop_border, use_image))
+        if not seen:
             raise ValueError("validate: no batches")
-        return {"psnr": float(torch.cat(vals).mean())}
+        res = {}
+        if want_psnr:
+            res["psnr"] = float(torch.cat(vals).mean())
+        if want_ssim:
+            res["ssim"] = float(torch.cat(ssims).mean())
+        return res
 
 
 # ------------------------------------------------------------------ ASDQE (Train/ASDQE.py)
@@ -1160,24 +1183,27 @@ class KDLAETrainer(_TrainingState):
                 self.theta_ema[off:off + n].copy_(sd[k].detach().reshape(-1))
 
     @torch.no_grad()
-    def validate(self, batches, window_size=8, crop_border=0, use_image=False, use_ema=None):
+    def validate(self, batches, window_size=8, crop_border=0, use_image=False, use_ema=None, metrics=("psnr",)):
         """ImageCleanModel.nondist_validation with pad_test (image_restoration_model.py:226-348) over
         ``(lq, gt)`` pairs, ``lq = {'img', 'denoise_rate'}``, ``gt = {'hq', 'sr'}``: reflect-pad ``img`` and the
         rate map right and bottom to a multiple of ``window_size``, run the inference engine
         (``kdlae_t_forward``), and take the PSNR of the top-left h x w window of ``hq`` (2h x 2w of ``sr``)
         against its target.  Returns ``{'psnr_hq': mean, 'psnr_sr': mean}`` over all images (``psnr_sr`` only
-        when ``static == 'train'``).
+        when ``static == 'train'``).  ``metrics``: ``"psnr"`` and / or ``"ssim"`` (the val.metrics names
+        calculate_psnr / calculate_ssim, :324-336); with ``"ssim"`` the result also holds ``ssim_hq`` / ``ssim_sr``
+        over the same windows.
 
         ``use_ema=None``: the EMA weights when ``ema_decay > 0`` (net_g_ema, :242-248), else the live ones.
         The chosen flat vector is packed straight into the module's inference handle; the trainer's buffers,
         the training engine and the module's parameters are not written, so training continues bit for bit."""
-        from .metrics import psnr_batch
+        from .metrics import psnr_batch, ssim_batch
+        want_psnr, want_ssim = _val_metrics(metrics)
         if use_ema is None:
             use_ema = self.theta_ema is not None
         if use_ema and self.theta_ema is None:
             raise RuntimeError("ema_decay is 0: there is no EMA copy to validate")
         flat = _inference_flat(self, self.theta_ema if use_ema else self.theta)
-        hqs, srs = [], []
+        hqs, srs, s_hqs, s_srs, seen = [], [], [], [], False
         for lq, gt in batches:
             img = lq["img"]
             if img.device.type != "cuda":
@@ -1191,14 +1217,19 @@ class KDLAETrainer(_TrainingState):
             # the last item's cropped outputs (pad_test's self.output, :236-237), as views
             self.val_output = {"hq": out["hq"][..., :h, :w],
                                "sr": out["sr"][..., :2 * h, :2 * w] if out["sr"] is not None else None}
-            hqs.append(psnr_batch(out["hq"], gt["hq"].to(img.device), (h, w), crop_border, use_image))
-            if out["sr"] is not None:
-                srs.append(psnr_batch(out["sr"], gt["sr"].to(img.device), (2 * h, 2 * w), crop_border, use_image))
-        if not hqs:
+            seen = True
+            for want, fn, a_hq, a_sr in ((want_psnr, psnr_batch, hqs, srs), (want_ssim, ssim_batch, s_hqs, s_srs)):
+                if not want:
+                    continue
+                a_hq.append(fn(out["hq"], gt["hq"].to(img.device), (h, w), crop_border, use_image))
+                if out["sr"] is not None:
+                    a_sr.append(fn(out["sr"], gt["sr"].to(img.device), (2 * h, 2 * w), crop_border, use_image))
+        if not seen:
             raise ValueError("validate: no batches")
-        res = {"psnr_hq": float(torch.cat(hqs).mean())}
-        if srs:
-            res["psnr_sr"] = float(torch.cat(srs).mean())
+        res = {}
+        for name, vals in (("psnr_hq", hqs), ("psnr_sr", srs), ("ssim_hq", s_hqs), ("ssim_sr", s_srs)):
+            if vals:
+                res[name] = float(torch.cat(vals).mean())
         return res
 
     def _distributed(self) -> bool:
