@@ -440,6 +440,37 @@ int kdlae_metric_ssim(const float* pred, const float* gt, int B, int C, int Hs, 
                       int h, int w, int crop_border, int mode, int variant,
                       double* out, void* scratch, void* stream);
 
+/* ---- Progressive-learning batch preparation (augment.hip).  Replaces the host loop between the data loader and
+ * feed_train_data (Train/basicsr/train.py:374-448): the stage's sub-batch (random.sample), one crop window for
+ * the whole batch, and the Bernoulli input mask of paired_image_dataset.py:19-36 (a kept pixel comes back bit
+ * for bit, a masked one becomes -value, not 0).  The stage rule and the host draws stay with the caller
+ * (augment.py); one launch serves every tensor of the batch (img, denoise_rate, hq, sr):
+ *   dst[b, c, i, j] = keep ? src[index[b], c, y0 + i, x0 + j] : -value
+ * The mask bit is keep[b, c, i, j] when `keep` is given (the bit-comparable route: the caller draws it as the
+ * reference does), else Philox4x32-10 with key = (seed lo, seed hi) and counter = (q lo, q hi, call lo, call hi),
+ * q = e / 4 for the linear index e into that segment's dst; element e takes word e % 4, u = (word >> 8) * 2^-24
+ * and keep = u >= prob, both in fp32.  Segment s of one call uses call + s.  Nothing synchronises, allocates or
+ * uses atomics; element indices are 64-bit; src is never written.  An index entry outside [0, B_src) is the
+ * caller's responsibility.  Errors are found before any launch. */
+typedef struct {
+  const float* src;      /* [B_src, C, Hs, Ws] contiguous fp32 */
+  float* dst;            /* [B, C, h, w] contiguous */
+  int B_src, C, Hs, Ws, h, w, y0, x0;   /* window rows y0..y0+h of dim 2, cols x0..x0+w of dim 3 */
+  float prob;            /* <= 0: plain copy; >= 1: every pixel masked */
+  const uint8_t* keep;   /* nullable [B, C, h, w], 1 = keep; null with prob > 0: Philox */
+} kdlae_prep_seg;
+int kdlae_train_prepare(const kdlae_prep_seg* segs, int nseg /* 1..4 */, const int* index /* device int[B], null = identity */,
+                        int B, float value, uint64_t seed, uint64_t call, void* stream);
+/* The per-frame rule of Dataset_PairedMutiImage (paired_image_dataset.py:219-272) over src, dst [B, F, H, W]
+ * (dst != src, F <= 16): frame f is masked with probs[f] as above (<= 0 copies, >= 1 masks every pixel; keep
+ * [B, F, H, W] or Philox over the linear index into dst).  interpolate != 0 (F odd): an odd frame f is the mask
+ * of 0.5f * (masked[f-1] + src[f+1]), one fp32 add then the multiply: the reference works in place in frame
+ * order, so frame f-1 is already masked when f reads it and frame f+1 is not.  masked[f-1] is recomputed from
+ * src and frame f-1's own mask bit; dst is never read. */
+int kdlae_train_mask_frames(const float* src, float* dst, int B, int F, int H, int W,
+                            const float* probs /* host float[F] */, int interpolate, float value,
+                            const uint8_t* keep /* nullable [B, F, H, W] */, uint64_t seed, uint64_t call, void* stream);
+
 /* ---- Kernel self-test entry points (not part of the drop-in boundary; nothing here is on a forward
  * or training path).  tests/test_kernel_variants*_gpu.py: kdlae_debug_tgemm, kdlae_debug_gemm,
  * kdlae_debug_gram, kdlae_debug_ln, kdlae_debug_small_in, kdlae_debug_bn;

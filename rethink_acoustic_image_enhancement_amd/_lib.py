@@ -53,6 +53,7 @@ EXPORTS = (
     "kdlae_debug_bn",
     "kdlae_metric_scratch_bytes", "kdlae_metric_psnr",
     "kdlae_metric_ssim_scratch_bytes", "kdlae_metric_ssim",
+    "kdlae_train_prepare", "kdlae_train_mask_frames",
     "kdlae_debug_train", "kdlae_debug_train_blocks", "kdlae_debug_train_s",
     "kdlae_debug_infer",
 )
@@ -124,6 +125,14 @@ class InferDesc(ctypes.Structure):
                 ("out_mode", c_int), ("nout", c_int), ("use_wp3", c_int),
                 ("out_nchw", c_int), ("wt", c_int), ("slots", c_int),
                 ("M", c_int), ("N1", c_int), ("N2", c_int)]
+
+
+class PrepSeg(ctypes.Structure):
+    """kdlae_prep_seg (include/kdlae.h): one tensor of a kdlae_train_prepare call."""
+
+    _fields_ = [("src", c_void_p), ("dst", c_void_p),
+                ("B_src", c_int), ("C", c_int), ("Hs", c_int), ("Ws", c_int), ("h", c_int), ("w", c_int),
+                ("y0", c_int), ("x0", c_int), ("prob", ctypes.c_float), ("keep", c_void_p)]
 
 
 _lib = None
@@ -262,6 +271,11 @@ def lib() -> ctypes.CDLL:
     L.kdlae_metric_ssim_scratch_bytes.restype = c_int64
     L.kdlae_metric_ssim.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                     c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    L.kdlae_train_prepare.argtypes = [ctypes.POINTER(PrepSeg), c_int, c_void_p, c_int, c_float, ctypes.c_uint64,
+                                      ctypes.c_uint64, c_void_p]
+    L.kdlae_train_mask_frames.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                          ctypes.POINTER(c_float), c_int, c_float, c_void_p, ctypes.c_uint64,
+                                          ctypes.c_uint64, c_void_p]
     L.kdlae_debug_tgemm.argtypes = [c_void_p, c_void_p]
     for f in ("kdlae_debug_gemm", "kdlae_debug_gram", "kdlae_debug_ln", "kdlae_debug_small_in",
               "kdlae_debug_train", "kdlae_debug_train_s", "kdlae_debug_infer"):
