@@ -299,8 +299,10 @@ int kdlae_tt_mark_sync(kdlae_tt_handle* h, int j);
 
 /* replaces self.cri_pix(pred, self.gt) with L1LossSr(loss_weight=1, reduction='mean') (losses.py:159-170):
  * loss[0] = 0.5 l1(hq) + 0.25 l1(sr) + 0.25 (shadow(hq) + shadow(sr)); dhq / dsr receive its gradient
- * (the shadow terms binarise at 0.1 and carry none).  pred_sr NULL = no sr term.  scratch: device
- * buffer of kdlae_train_l1sr_scratch_floats() floats. */
+ * (the shadow terms binarise at 0.1 and carry none).  pred_sr NULL = no sr term.  dhq / dsr NULL =
+ * loss only: that gradient is not written.  pred_sr with gt_sr NULL or n_sr <= 0 is
+ * KDLAE_EINVAL_CONFIG, as is any other null required pointer or n_hq <= 0; nothing is launched.
+ * scratch: device buffer of kdlae_train_l1sr_scratch_floats() floats. */
 int64_t kdlae_train_l1sr_scratch_floats(void);
 int kdlae_train_l1sr(const float* pred_hq, const float* gt_hq, int64_t n_hq, const float* pred_sr,
                      const float* gt_sr, int64_t n_sr, float* dhq, float* dsr, float* loss, float* scratch,

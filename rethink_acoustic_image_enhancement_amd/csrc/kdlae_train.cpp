@@ -1352,6 +1352,7 @@ int64_t kdlae_train_l1sr_scratch_floats(void) { return 4 * 1024; }
 int kdlae_train_l1sr(const float* pred_hq, const float* gt_hq, int64_t n_hq, const float* pred_sr, const float* gt_sr,
                      int64_t n_sr, float* dhq, float* dsr, float* loss, float* scratch, void* stream) {
   if (!pred_hq || !gt_hq || !loss || !scratch || n_hq <= 0) return fail(KDLAE_EINVAL_CONFIG, "null argument");
+  if (pred_sr && (!gt_sr || n_sr <= 0)) return fail(KDLAE_EINVAL_CONFIG, "pred_sr without gt_sr / n_sr");
   hipStream_t s = (hipStream_t)stream;
   const int nb = 1024;
   float* p0 = scratch;

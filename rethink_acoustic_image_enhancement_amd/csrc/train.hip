@@ -1543,7 +1543,7 @@ __global__ __launch_bounds__(256) void l1sr_kernel(const float* __restrict__ pre
 __global__ void l1sr_final_kernel(const float* part0, int nblk0, double n0, float wl0, float ws0, const float* part1,
                                   int nblk1, double n1, float wl1, float ws1, float* out) {
   if (threadIdx.x != 0) return;
-  float a0 = 0.f, s0 = 0.f, a1 = 0.f, s1 = 0.f;
+  double a0 = 0.0, s0 = 0.0, a1 = 0.0, s1 = 0.0;  // as clip_coef_kernel / l1frames_final_kernel: no rounding per block
   for (int b = 0; b < nblk0; ++b) {
     a0 += part0[2 * b];
     s0 += part0[2 * b + 1];
@@ -1619,8 +1619,10 @@ hipError_t launch_clip_coef(const float* part, int nblk, float gscale, float max
 
 hipError_t launch_adamw(float* p, const float* g, float* m, float* v, long long n, const float* state, float lr,
                         float beta1, float beta2, float eps, float wd, int step, hipStream_t s) {
-  const float bc1 = 1.f - powf(beta1, (float)step);
-  const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
+  // in double, rounded once (torch forms both in double): 1 - beta2^step cancels in fp32, at step 2
+  // with beta2 = 0.999 one ulp of powf's result is 3e-5 of the difference
+  const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+  const float bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
   hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n, 256, 16384)), dim3(256), 0, s, p, g, m, v, n, state, lr, beta1,
                      beta2, eps, wd, bc1, bc2s);
   return hipGetLastError();
