@@ -539,7 +539,8 @@ int kdlae_debug_gemm_variant(int family, int i, int* v);
  * reduced[Bn * heads][Ch^2 + 2 Ch] (Gram in accumulator order: element (i * CT + j) * 256 + 4 l + e =
  * G[16 i + 4 (l / 16) + e][16 j + l % 16], CT = Ch / 16; then |q_c|^2, |k_c|^2).  partial: scratch of
  * partial_floats.  route 0: production (ring kernel where it applies), 1: without the ring kernel
- * (zeros ignored), 2: the generic 64-pixel-step kernel. */
+ * (zeros ignored), 2: the generic 64-pixel-step kernel, 3: the ring kernel without v (q | k only: v_out
+ * may be null and is not written; KDLAE_EINVAL_SHAPE where the ring kernel does not apply). */
 typedef struct kdlae_debug_gram_desc {
   const float* qkv; int ld;
   const float* wdw; const float* bdw;
@@ -706,7 +707,12 @@ int kdlae_debug_train_s(const kdlae_debug_train_s_desc* d, void* stream);
  *   op 7 conv3d_c16     in0 (16), w0 = [9 kt][64][4] fragments, bias0 [16], kt 1 / 3, relu -> out0 (16)
  *   op 8 maxpool2       in0 [Bn frames][H][W] (C) -> out0 [Bn][H/2][W/2] (C); C % 4 == 0
  *   op 9 gap + head     in0 [Bn][H W] (C), slots, scratch (Bn slots C floats), w0 [M][C], bias0 [M], w1 [N1][M],
- *                       bias1, w2 [N2][N1], bias2, w3 [N2], bias3 [1] -> out0 = score [Bn] */
+ *                       bias1, w2 [N2][N1], bias2, w3 [N2], bias3 [1] -> out0 = score [Bn]
+ *   op 10 attn_out_dw   in0 = v (C channels, ldi0 = its pixel stride, e.g. qkv + 2C with 3C), w0 = wdw [9][3C] and
+ *                       bias0 = bdw [3C] (or null) of the whole qkv_dwconv (v's part at channel 2C), w1 = M per image
+ *                       as attn_fold's split records, bias1 = project_out bias [C] (or null), R / ldr (may be out0),
+ *                       zeros (>= 16 zero floats) -> out0 = R + bias1 + M dw3x3(v); C in {48, 96}, W % 16 == 0, every
+ *                       view 16-byte aligned with ld % 4 == 0, out0 must not overlap in0 */
 typedef struct kdlae_debug_infer_desc {
   int op;
   const float* in[3]; int ldi[3];

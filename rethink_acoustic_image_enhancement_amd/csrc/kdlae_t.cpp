@@ -44,6 +44,10 @@ struct BlockW {
   // r06: MDTA pass 1 with LN + qkv recomputed on each tile's halo (mdta_fused.hip) for single-head
   // C = 48 / 96 blocks; opt-in (debug flag mdta_fusion), the qkv GEMM + Gram ring by default
   bool mdta_fused = false;
+  // v's depthwise 3x3 as the prologue of the attention-output product (attn_out_dw.hip) behind the Gram
+  // ring without v, on the blocks that take the fused feed-forward half; debug flag no_attn_out_dw keeps
+  // the v-writing ring + the per-image-weight GEMM (A/B baseline and bit-identity reference)
+  bool attn_out_dw = false;
 };
 
 }  // namespace kdlae
@@ -327,6 +331,7 @@ struct Packer {
     // opt-in (debug flag mdta_fusion): r06 measured it slower than the qkv GEMM + Gram ring it replaces
     // (C96@512^2 3.54 vs 3.41 ms, C48@1024^2 5.93 vs 5.29 ms; DESIGN.md §4 "Fused MDTA pass 1")
     b.mdta_fused = heads == 1 && (C == 48 || C == 96) && b.qkv.ntiles == 3 * C / 16 && debug_flag("mdta_fusion");
+    b.attn_out_dw = (C == 48 || C == 96) && b.Ch <= 96 && !debug_flag("no_attn_out_dw");
     return b;
   }
 
@@ -527,6 +532,7 @@ struct Fwd {
     const int nslots = nslots_for(Hh, Ww);
     const int nseg = Ww % 16 == 0 ? nslots / (Ww / 16) : 0;
     const int seg_rows = nseg ? (Hh + nseg - 1) / nseg : 0;
+    bool dw_out = false;  // no-v ring + attn_out_dw in place of the v-writing ring + the M GEMM
     if (b.mdta_fused && mdta_fused_supported(b.C, b.heads, Hh, Ww, nseg, seg_rows)) {
       // LN + qkv + dwconv + Gram in one pass (mdta_fused.hip): qkv never reaches HBM
       const int CT = b.Ch / 16;
@@ -559,6 +565,7 @@ struct Fwd {
       HIPCHK(launch_attn_fold(buf(pl.red), q.slot_floats, h->P(b.proj), h->P(b.temp), buf(pl.Mp), B, b.C, b.heads, s));
     } else {
     View qkv{buf(pl.qkv), 3 * b.C};
+    dw_out = ffn && b.attn_out_dw && attn_out_dw_supported(b.C, Hh, Ww, qkv.ld);
     rc = gemm(b.qkv, h->P3(b.qkv.w3), 0, x, Hh, Ww, qkv, 0, nullptr, 0, ln, b.C, b.C);
     if (rc) return rc;
     GramParams gp{};
@@ -579,10 +586,15 @@ struct Fwd {
     gp.zeros = h->P(h->zeros);
     const int CT = b.Ch / 16;
     gp.slot_floats = CT * CT * 256 + 2 * b.Ch;
+    dw_out = dw_out && gram_ring_applies(gp);
+    gp.no_v = dw_out ? 1 : 0;
     if ((rc = probe_begin(2, b.C))) return rc;
-    tag = "gram C" + std::to_string(b.C) + " Ch" + std::to_string(b.Ch) + " HW" + std::to_string(HW);
+    tag = "gram C" + std::to_string(b.C) + " Ch" + std::to_string(b.Ch) + " HW" + std::to_string(HW) + (dw_out ? " qk" : "");
     HIPCHK(launch_dwconv_gram(gp, s));
-    if ((rc = probe_end(2, b.C, 4.0 * P * 4 * b.C, 2.0 * P * (27.0 * b.C + (double)b.C * b.Ch)))) return rc;
+    // algorithmic: read q | k | v, write v; without v read q | k only
+    rc = dw_out ? probe_end(2, b.C, 4.0 * P * 2 * b.C, 2.0 * P * (18.0 * b.C + (double)b.C * b.Ch))
+                : probe_end(2, b.C, 4.0 * P * 4 * b.C, 2.0 * P * (27.0 * b.C + (double)b.C * b.Ch));
+    if (rc) return rc;
     HIPCHK(launch_gram_reduce(gp.partial, buf(pl.red), B, b.heads, gp.nslots, gp.slot_floats, s));
     HIPCHK(launch_attn_fold(buf(pl.red), gp.slot_floats, h->P(b.proj), h->P(b.temp), buf(pl.Mp), B, b.C, b.heads, s));
     }
@@ -626,6 +638,34 @@ struct Fwd {
                   0, ln, b.C, b.C);
         if (rc) return rc;
       }
+    } else if (dw_out) {
+      // x1 = x + M dw3x3(v) in place, v read where the qkv GEMM left it: vbuf is not touched
+      AttnOutDwParams q{};
+      q.v = buf(pl.qkv) + 2 * b.C;
+      q.ldv = 3 * b.C;
+      q.wdw = h->P(b.dwqkv) + 2 * b.C;
+      q.ldw = 3 * b.C;
+      q.bdw = b.dwqkv_b != kNone ? h->P(b.dwqkv_b) + 2 * b.C : nullptr;
+      q.M = buf(pl.Mp);
+      q.m_img_stride = split3_floats(b.C / 16, b.C / 16);
+      q.bias = h->P(b.proj_gemm.bias);
+      q.R = x.p;
+      q.ldr = x.ld;
+      q.out = x.p;
+      q.ldo = x.ld;
+      q.Bn = B;
+      q.H = Hh;
+      q.W = Ww;
+      q.zeros = h->P(h->zeros);
+      if ((rc = probe_begin(1, b.C))) return rc;
+      if (h->probe_class == 1)
+        tag = "attn_out_dw C" + std::to_string(b.C) + " HW" + std::to_string(HW) + " N" + std::to_string(b.C) + " K" +
+              std::to_string(b.C) + " res";
+      HIPCHK(launch_attn_out_dw(q, b.C, s));
+      const double Pd = (double)P;
+      // algorithmic: read v and x, write x1; M per image; the stencil's and the product's FLOPs
+      if ((rc = probe_end(1, b.C, 4.0 * (Pd * 3.0 * b.C + (double)B * b.C * b.C), 2.0 * Pd * (9.0 * b.C + (double)b.C * b.C))))
+        return rc;
     } else {
       rc = gemm(b.proj_gemm, buf(pl.Mp), split3_floats(b.C / 16, b.C / 16), View{buf(pl.vbuf), b.C}, Hh, Ww, x, 0,
                 x.p, x.ld, 0,

@@ -59,6 +59,8 @@ struct GramParams {
   int Bn, H, W;
   int nslots, slot_floats;
   const float* zeros;              // >= 16 zero floats (DMA source for padding); null -> no ring kernel
+  int no_v;                        // 1: q | k only (ring kernel, else an error): v is neither read nor written and
+                                   // v_out may be null; its stencil runs in launch_attn_out_dw's kernel
 };
 
 struct GateParams {
@@ -106,6 +108,7 @@ bool gemm_has_variant2(int NT, int KG, bool conv3, int out_mode);  // r02 chunke
 hipError_t launch_ln_stats(const float* x, int ld, int C, long long P, float* stats, hipStream_t s);
 hipError_t launch_dwconv_gram(const GramParams& p, hipStream_t s);
 hipError_t launch_dwconv_gram_route(const GramParams& p, int route, hipStream_t s);  // 2: generic kernel
+bool gram_ring_applies(const GramParams& p);  // route 0 takes the LDS-DMA ring kernel (needed for no_v)
 hipError_t launch_gram_reduce(const float* partial, float* reduced, int Bn, int heads, int nslots,
                               int slot_floats, hipStream_t s);
 hipError_t launch_attn_fold(const float* reduced, int slot_floats, const float* proj, const float* temp,
@@ -133,6 +136,26 @@ struct GdfnParams {
 };
 bool gdfn_supported(int C, int hidS);
 hipError_t launch_gdfn_out(const GdfnParams& p, int C, hipStream_t s);
+
+// Attention output with the depthwise 3x3 of v as its prologue (attn_out_dw.hip), C = 48 / 96:
+//   out = R + bias + M_img . dw3x3(v)        (Attention.forward :140-144 + the block's residual :160)
+// v is read where the qkv GEMM left it (a strided view of the qkv buffer), so with the no-v Gram ring the
+// MDTA sequence is: qkv GEMM -> launch_dwconv_gram (no_v) -> launch_gram_reduce -> launch_attn_fold ->
+// launch_attn_out_dw, and v' = dw3x3(v) never reaches HBM.  Same bits as the v-writing ring followed by
+// the per-image-weight gemm_res_kernel (dw3.h's stencil order, mfma3.h's split and term order).
+struct AttnOutDwParams {
+  const float* v; int ldv;         // [P][ldv], C channels (qkv + 2C, ldv = 3C); 16-byte aligned, ldv % 4 == 0
+  const float* wdw; int ldw;       // v's depthwise weights, tap t of channel c at wdw[t * ldw + c]
+  const float* bdw;                // [C] or null
+  const float* M; long long m_img_stride;  // attn_fold's split records [C/16][ceil(C/32)][kRec3] per image
+  const float* bias;               // project_out bias [C] or null
+  const float* R; int ldr;         // residual (may alias out)
+  float* out; int ldo;             // must not overlap v (neighbouring strips read v as halo)
+  int Bn, H, W;                    // W % 16 == 0
+  const float* zeros;              // >= 16 zero floats (source of out-of-image halo lines)
+};
+bool attn_out_dw_supported(int C, int H, int W, int ldv);
+hipError_t launch_attn_out_dw(const AttnOutDwParams& p, int C, hipStream_t s);
 
 // Fused feed-forward half (ffn.hip): out = x + project_out(gate(dwconv(project_in(LN(x))))) for C = 48 /
 // 96 — project_in recomputed on each tile's halo, so its 2 hidS-wide rows never reach HBM.  `out` must

@@ -19,6 +19,7 @@
 #include "kernels.h"
 #include "mfma3.h"
 #include "lds_dma.h"
+#include "dw3.h"
 
 namespace kdlae {
 
@@ -136,13 +137,12 @@ __global__ __launch_bounds__(256) void dwconv_gram_kernel(GramParams p) {
         const float bias = p.bdw ? p.bdw[c] : 0.f;
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-          float a = bias;
-#pragma unroll
-          for (int t = 0; t < 9; ++t) {
+          float a = dw3x3(bias, w, [&](int r, int dx) {
+            const int t = 3 * r + dx;
             const bool ok = (okm[s] >> t) & 1u;
             const float xv = X[(ok ? base[s] + dofs[t] : 0) + c];
-            a = fmaf(ok ? xv : 0.f, w[t], a);
-          }
+            return ok ? xv : 0.f;
+          });
           const int pix = u * 16 + 4 * lq + s;
           const bool valid = pix < HW;
           a = valid ? a : 0.f;
@@ -301,11 +301,7 @@ __global__ __launch_bounds__(64 * gram_waves(CT)) void dwconv_gram_sweep_kernel(
         const int ct = (wave + NW * j) % CT;
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-          float a = bias[j];
-#pragma unroll
-          for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int dx = 0; dx < 3; ++dx) a = fmaf(win[j][r][s + dx], w[j][3 * r + dx], a);
+          const float a = dw3x3(bias[j], w[j], [&](int r, int dx) { return win[j][r][s + dx]; });
           const int lp = 4 * lq + s;
           if (part[j] == 0) {
             qs[buf][lp * S + ct * 16 + li] = a;
@@ -363,7 +359,7 @@ __global__ __launch_bounds__(64 * gram_waves(CT)) void dwconv_gram_sweep_kernel(
 // pipelined by one row: iteration y runs the Gram MFMAs of row y (staging buffer buf) interleaved,
 // per k-step, with the depthwise stencil of row y+1 (ring rows y..y+2 -> buffer buf^1), while rows
 // y+3, y+4 are in flight and row y+5 is issued.  One barrier per row.
-//  * ring row = 18 pixels (strip columns -1..16) x [q | k | v of this head | 1 pad float4];
+//  * ring row = 18 pixels (strip columns -1..16) x [q | k | v of this head | 1 pad float4] (NOV: q | k);
 //    the pad makes the pixel stride 3 Ch + 4 floats, so the stencil's column reads (16 channels x
 //    4 pixel groups per wave) fall on 64 distinct banks.  Pad items and out-of-image pixels read
 //    p.zeros;
@@ -381,12 +377,16 @@ __device__ __forceinline__ void for_each_int(std::integer_sequence<int, J...>, F
   (f(std::integral_constant<int, J>{}), ...);
 }
 
-template <int CT>
+// NOV ("no v"): the ring row holds q | k only and there are no v jobs: every wave is a DMA wave, v_out
+// is not touched (the attention-output kernel of attn_out_dw.hip applies v's stencil itself).  Jobs,
+// Gram tiles and waves are dealt as with v, so the Gram partials and norms are the same bits.
+template <int CT, bool NOV = false>
 struct GramRing {
   static constexpr int Ch = CT * 16;
   static constexpr int NW = gram_ring_waves(CT);
-  static constexpr int NJ = 3 * CT;
-  static constexpr int PS4 = 3 * Ch / 4 + 1;          // float4 per ring pixel
+  static constexpr int NP = NOV ? 2 : 3;              // parts in a ring pixel
+  static constexpr int NJ = NP * CT;
+  static constexpr int PS4 = NP * Ch / 4 + 1;         // float4 per ring pixel
   static constexpr int PS = 4 * PS4;                  // floats per ring pixel
   static constexpr int Items = 18 * PS4;
   static constexpr int Pieces = (Items + 63) / 64;    // 1 KiB DMA wave-instructions per row
@@ -438,9 +438,9 @@ struct GramRing {
 };
 
 constexpr auto KDLAE_RING_XCD = 1;
-template <int CT>
+template <int CT, bool NOV = false>
 __global__ __launch_bounds__(64 * gram_ring_waves(CT)) void dwconv_gram_ring_kernel(GramParams p, int seg_rows) {
-  using R = GramRing<CT>;
+  using R = GramRing<CT, NOV>;
   using dma::f32x4;
   constexpr int NW = R::NW, NJ = R::NJ, NDW = R::NDW, PPD = R::PPD;
   constexpr int Ch = R::Ch, S = R::S, PS = R::PS, PS4 = R::PS4;
@@ -467,7 +467,7 @@ __global__ __launch_bounds__(64 * gram_ring_waves(CT)) void dwconv_gram_ring_ker
   const int HW = p.H * p.W;
   const int C = p.C;
   const float* __restrict__ X = p.qkv + (long long)b * HW * p.ld;
-  float* __restrict__ V = p.v_out + (long long)b * HW * p.ldv;
+  float* __restrict__ V = NOV ? nullptr : p.v_out + (long long)b * HW * p.ldv;
   const int xs = strip * 16;
   const int y0 = seg * seg_rows, y1 = min(y0 + seg_rows, p.H);
 
@@ -562,11 +562,7 @@ __global__ __launch_bounds__(64 * gram_ring_waves(CT)) void dwconv_gram_ring_ker
         constexpr int K = R::job_kind(D, j);
         if constexpr (K != 0) {
           if (R::job_all(D, j) || wave + NW * j < NJ) {
-            float a = bias[j];
-#pragma unroll
-            for (int rr = 0; rr < 3; ++rr)
-#pragma unroll
-              for (int dx = 0; dx < 3; ++dx) a = fmaf(win[j][rr][s + dx], w[j][3 * rr + dx], a);
+            const float a = dw3x3(bias[j], w[j], [&](int rr, int dx) { return win[j][rr][s + dx]; });
             auto to_lds = [&]() {
               float* dst = part[j] == 0 ? qs : ks;
               dst[sb * 16 * S + lp * S + ctj[j] * 16 + li] = a;
@@ -629,7 +625,7 @@ __global__ __launch_bounds__(64 * gram_ring_waves(CT)) void dwconv_gram_ring_ker
     }
   };
   constexpr int PX = R::Pieces % NDW;  // DMA ranks below PX issue PPD pieces, the rest PPD - 1
-  if (!dma_wave) run(std::false_type{}, std::integral_constant<int, 0>{});
+  if (!NOV && !dma_wave) run(std::false_type{}, std::integral_constant<int, 0>{});
   else if (PX == 0 || drank < PX) run(std::true_type{}, std::integral_constant<int, PPD>{});
   else run(std::true_type{}, std::integral_constant<int, (PX == 0 ? PPD : PPD - 1)>{});
 
@@ -651,6 +647,8 @@ __global__ __launch_bounds__(64 * gram_ring_waves(CT)) void dwconv_gram_ring_ker
   for (int idx = threadIdx.x; idx < 2 * Ch; idx += 64 * NW) out[CT * CT * 256 + idx] = nred[idx];
 }
 
+bool gram_ring_applies(const GramParams& p);
+
 // generic: the 64-pixel-step kernel whatever the width (self-test route; production takes it only
 // for W % 16 != 0 or a slot count that does not tile the strips)
 template <int CT>
@@ -660,13 +658,15 @@ static void launch_gram_ct(const GramParams& p, bool generic, hipStream_t s) {
     return;
   }
   if constexpr (CT <= 6) {
-    using R = GramRing<CT>;
-    if (p.zeros && p.W % 16 == 0 && p.nslots % (p.W / 16) == 0 && p.ld % 4 == 0 && p.C % 4 == 0 &&
-        (unsigned long long)p.H * p.W * p.ld * 4 < (1ull << 32)) {
+    if (gram_ring_applies(p)) {
       const int nseg = p.nslots / (p.W / 16);
       const int seg_rows = (p.H + nseg - 1) / nseg;
-      hipLaunchKernelGGL(dwconv_gram_ring_kernel<CT>, dim3(p.nslots, p.heads, p.Bn), dim3(64 * gram_ring_waves(CT)),
-                         R::lds_bytes, s, p, seg_rows);
+      if (p.no_v)
+        hipLaunchKernelGGL((dwconv_gram_ring_kernel<CT, true>), dim3(p.nslots, p.heads, p.Bn),
+                           dim3(64 * gram_ring_waves(CT)), (GramRing<CT, true>::lds_bytes), s, p, seg_rows);
+      else
+        hipLaunchKernelGGL((dwconv_gram_ring_kernel<CT, false>), dim3(p.nslots, p.heads, p.Bn),
+                           dim3(64 * gram_ring_waves(CT)), (GramRing<CT, false>::lds_bytes), s, p, seg_rows);
       return;
     }
   }
@@ -682,8 +682,15 @@ static void launch_gram_ct(const GramParams& p, bool generic, hipStream_t s) {
 
 hipError_t launch_dwconv_gram(const GramParams& p, hipStream_t s) { return launch_dwconv_gram_route(p, 0, s); }
 
+// the LDS-DMA ring kernel takes this launch (the only kernel of the family with a no-v form)
+bool gram_ring_applies(const GramParams& p) {
+  return p.Ch % 16 == 0 && p.Ch <= 96 && p.zeros && p.W % 16 == 0 && p.nslots % (p.W / 16) == 0 && p.ld % 4 == 0 &&
+         p.C % 4 == 0 && (unsigned long long)p.H * p.W * p.ld * 4 < (1ull << 32);
+}
+
 hipError_t launch_dwconv_gram_route(const GramParams& p, int route, hipStream_t s) {
   const bool g = route == 2;
+  if (p.no_v && (g || !gram_ring_applies(p))) return hipErrorInvalidValue;  // no other kernel leaves v out
   switch (p.Ch / 16) {
     case 1: launch_gram_ct<1>(p, g, s); break;
     case 2: launch_gram_ct<2>(p, g, s); break;

@@ -162,11 +162,12 @@ extern "C" int kdlae_debug_gemm(const kdlae_debug_gemm_desc* d, void* stream) {
 }
 
 extern "C" int kdlae_debug_gram(const kdlae_debug_gram_desc* d, void* stream) {
-  if (!d || !d->qkv || !d->wdw || !d->v_out || !d->partial || !d->reduced) return fail(KDLAE_EINVAL_CONFIG, "null operand");
+  if (!d || d->route < 0 || d->route > 3) return fail(KDLAE_EINVAL_CONFIG, "null descriptor or route not 0..3");
+  const bool no_v = d->route == 3;  // the q | k ring: v_out is neither needed nor touched
+  if (!d->qkv || !d->wdw || (!no_v && !d->v_out) || !d->partial || !d->reduced) return fail(KDLAE_EINVAL_CONFIG, "null operand");
   if (d->heads < 1 || d->C % d->heads || (d->C / d->heads) % 16 || d->C / d->heads > 128 || d->Bn < 1 || d->H < 1 ||
-      d->W < 1 || d->ld < 3 * d->C || d->ldv < d->C)
+      d->W < 1 || d->ld < 3 * d->C || (!no_v && d->ldv < d->C))
     return fail(KDLAE_EINVAL_SHAPE, "bad Gram geometry (Ch = C / heads must be 16..128, a multiple of 16)");
-  if (d->route < 0 || d->route > 2) return fail(KDLAE_EINVAL_CONFIG, "route must be 0..2");
   kdlae::GramParams p{};
   p.qkv = d->qkv;
   p.ld = d->ld;
@@ -184,11 +185,14 @@ extern "C" int kdlae_debug_gram(const kdlae_debug_gram_desc* d, void* stream) {
   p.nslots = kdlae::nslots_for(d->H, d->W);  // the engine's slot count
   const int CT = p.Ch / 16;
   p.slot_floats = CT * CT * 256 + 2 * p.Ch;
-  p.zeros = d->route == 0 ? d->zeros : nullptr;
+  p.zeros = (d->route == 0 || no_v) ? d->zeros : nullptr;
+  p.no_v = no_v ? 1 : 0;
   if ((long long)d->Bn * d->heads * p.nslots * p.slot_floats > d->partial_floats)
     return fail(KDLAE_EINVAL_SHAPE, "partial scratch too small");
+  if (no_v && !kdlae::gram_ring_applies(p))
+    return fail(KDLAE_EINVAL_SHAPE, "route 3 (no v) needs the ring kernel: zeros, W % 16 == 0, ld % 4 == 0, Ch <= 96");
   hipStream_t s = (hipStream_t)stream;
-  HIPCHK(kdlae::launch_dwconv_gram_route(p, d->route, s));
+  HIPCHK(kdlae::launch_dwconv_gram_route(p, no_v ? 0 : d->route, s));
   HIPCHK(kdlae::launch_gram_reduce(p.partial, d->reduced, d->Bn, d->heads, p.nslots, p.slot_floats, s));
   return KDLAE_OK;
 }
@@ -730,7 +734,31 @@ extern "C" int kdlae_debug_infer(const kdlae_debug_infer_desc* d, void* stream) 
       e = kdlae::launch_asdqe_head(p, s);
       break;
     }
-    default: return fail(KDLAE_EINVAL_CONFIG, "op must be 0..9");
+    case 10: {  // attention output with the depthwise 3x3 of v as its prologue
+      if (!d->in[0] || !d->w[0] || !d->w[1] || !d->R || !d->out[0] || !d->zeros) return fail(KDLAE_EINVAL_CONFIG, null_op);
+      if (C != 48 && C != 96) return fail(KDLAE_EINVAL_SHAPE, "attn_out_dw: C in {48, 96}");
+      if (d->W % 16) return fail(KDLAE_EINVAL_SHAPE, "attn_out_dw: W % 16 == 0");
+      if (!in4(0) || !out4(0) || !al16(d->R) || d->ldr % 4 || !al16(d->w[0]) || !al16(d->w[1]) || !al16(d->bias[0]) ||
+          !al16(d->bias[1]))
+        return fail(KDLAE_EINVAL_SHAPE, align);
+      if (!geo || F != 1 || !in_ok(0, C, px) || !out_ok(0, C, px) || d->ldr < C || px * d->ldr >= kMaxIdx ||
+          !kdlae::attn_out_dw_supported(C, d->H, d->W, d->ldi[0]) ||
+          !img_bytes_ok(d->H, d->W, std::max(d->ldr, d->ldo[0])))
+        return fail(KDLAE_EINVAL_SHAPE, bad);
+      {  // neighbouring strips read v as halo: out must not overlap it
+        const uintptr_t v0 = (uintptr_t)d->in[0], v1 = v0 + ((size_t)(px - 1) * d->ldi[0] + C) * 4;
+        const uintptr_t o0 = (uintptr_t)d->out[0], o1 = o0 + ((size_t)(px - 1) * d->ldo[0] + C) * 4;
+        if (v0 < o1 && o0 < v1) return fail(KDLAE_EINVAL_SHAPE, "attn_out_dw: out must not overlap v");
+      }
+      kdlae::AttnOutDwParams p{};
+      p.v = d->in[0]; p.ldv = d->ldi[0]; p.wdw = d->w[0] + 2 * C; p.ldw = 3 * C; p.bdw = d->bias[0] ? d->bias[0] + 2 * C : nullptr;
+      p.M = d->w[1]; p.m_img_stride = kdlae::split3_floats(C / 16, C / 16); p.bias = d->bias[1];
+      p.R = d->R; p.ldr = d->ldr; p.out = d->out[0]; p.ldo = d->ldo[0];
+      p.Bn = d->Bn; p.H = d->H; p.W = d->W; p.zeros = d->zeros;
+      e = kdlae::launch_attn_out_dw(p, C, s);
+      break;
+    }
+    default: return fail(KDLAE_EINVAL_CONFIG, "op must be 0..10");
   }
   if (e != hipSuccess) return fail(KDLAE_EHIP, std::string("kdlae_debug_infer: ") + hipGetErrorString(e));
   return KDLAE_OK;
