@@ -473,6 +473,59 @@ int kdlae_train_mask_frames(const float* src, float* dst, int B, int F, int H, i
                             const float* probs /* host float[F] */, int interpolate, float value,
                             const uint8_t* keep /* nullable [B, F, H, W] */, uint64_t seed, uint64_t call, void* stream);
 
+/* ---- Dataset sample transforms (csrc/data.hip): the per-sample work of Dataset_SuperRestoration_param and
+ * Dataset_PairedMutiImage (Train/basicsr/data/paired_image_dataset.py:902-982, 160-294) between image decode and
+ * the batch: pad, crop, noise, flips / rotations, layout, normalisation.  Plain streaming kernels; nothing
+ * synchronises or allocates; element indices are 64-bit; errors are found before any launch.
+ *
+ * One item = one source image and one destination slot.  The source (u8 or fp32, element strides sy, sx, sc, so
+ * HWC-interleaved and CHW-planar both fit) sits on a virtual canvas: centred on Hc x Wc with zeros around it
+ * (top = (Hc - Hs) / 2, left = (Wc - Ws) / 2: pad_image), then extended at the bottom / right to Hp x Wp by
+ * reflect101 (cv2.BORDER_REFLECT_101, numpy 'reflect') or symmetric (cv2.BORDER_REFLECT, numpy 'symmetric'); the
+ * reflection sees the zero-padded canvas and repeats for pads longer than the canvas.  Window (top, left, h, w)
+ * on that canvas; the dihedral code (bit 2 transpose, bit 1 flip rows, bit 0 flip columns) maps it to dst
+ * [C, h', w'] = transpose?(flip_cols?(flip_rows?(window))), (h', w') = (w, h) with a transpose; reverse_c stores
+ * source channel c at C - 1 - c.  Value: u8 -> float(v) / 255.0f (one fp32 division); with noise
+ * float(clip(double(x) + (loc + scale * z / div), 0, 1)), every step a rounded fp64 operation in this order, z
+ * taken at the window coordinate (i, j, c) BEFORE the dihedral map and the channel reversal from the fp64 array z
+ * [h, w, C] (noise = 1) or from Philox4x32-10 (noise = 2: key = seed, counter = (e / 2, call + item number),
+ * e = (i * w + j) * C + c, words (0, 1) for an even e and (2, 3) for an odd one, u1 = ((w0 >> 8) + 1) * 2^-24,
+ * u2 = (w1 >> 8) * 2^-24, z = sqrtf(-2 logf(u1)) * cosf(2 pi u2) in fp32); with `counts` the noise applies only
+ * when (double)max(counts[0], counts[1]) / count_n > count_thr, decided on the device; then (x - mean[c']) / std[c']
+ * in fp32 by destination channel where given (each nullable).  dst must not overlap src.  `items` is a host
+ * table; it is validated, copied to `table` (device, n_items * sizeof(kdlae_data_item) bytes) on the stream and
+ * served by one launch. */
+typedef struct {
+  const void* src;        /* device, u8 or fp32 */
+  float* dst;             /* device fp32 [C, h', w'] contiguous */
+  const double* z;        /* device fp64 [h, w, C], noise == 1 */
+  const int32_t* counts;  /* nullable device int32[2] of kdlae_data_count: the noise is conditional */
+  const float* mean;      /* nullable device fp32 [C] */
+  const float* std;       /* nullable device fp32 [C] */
+  int64_t sy, sx, sc;     /* source element strides of row, column, channel */
+  int64_t count_n;
+  double count_thr;
+  double loc, scale, div;
+  int src_u8;             /* 1: u8 source, 0: fp32 */
+  int Hs, Ws, C;
+  int Hc, Wc, Hp, Wp;
+  int pad_mode;           /* 0 none (Hp x Wp == Hc x Wc), 1 reflect101, 2 symmetric */
+  int top, left, h, w;
+  int dihedral;           /* 0..7 */
+  int reverse_c;
+  int noise;              /* 0 off, 1 z array, 2 Philox */
+  int reserved;
+} kdlae_data_item;
+int kdlae_data_sample(const kdlae_data_item* items /* host */, void* table /* device */, int n_items, uint64_t seed,
+                      uint64_t call, void* stream);
+/* counts[b] = (number of x[b, :] == 0.0f, number == 1.0f) over x [B, n_per_sample]; integer adds only, so the
+ * result does not depend on the order; counts is zeroed here.  -0.0f counts as zero. */
+int kdlae_data_count(const float* x, int B, int64_t n_per_sample, int32_t* counts /* device [B][2] */, void* stream);
+/* In place over x [B, C, hw]: where (double)max(counts[b]) / (C * hw) > thr, x = x + nudge (one fp32 add: the
+ * reference's `img_lq + 1e-14` moves exact zeros only); then (x - mean[c]) / std[c] where given (device, nullable). */
+int kdlae_data_finish(float* x, int B, int C, int64_t hw, const int32_t* counts, double thr, float nudge,
+                      const float* mean, const float* std, void* stream);
+
 /* ---- Kernel self-test entry points (not part of the drop-in boundary; nothing here is on a forward
  * or training path).  tests/test_kernel_variants*_gpu.py: kdlae_debug_tgemm, kdlae_debug_gemm,
  * kdlae_debug_gram, kdlae_debug_ln, kdlae_debug_small_in, kdlae_debug_bn;

@@ -54,6 +54,7 @@ EXPORTS = (
     "kdlae_metric_scratch_bytes", "kdlae_metric_psnr",
     "kdlae_metric_ssim_scratch_bytes", "kdlae_metric_ssim",
     "kdlae_train_prepare", "kdlae_train_mask_frames",
+    "kdlae_data_sample", "kdlae_data_count", "kdlae_data_finish",
     "kdlae_debug_train", "kdlae_debug_train_blocks", "kdlae_debug_train_s",
     "kdlae_debug_infer",
 )
@@ -133,6 +134,18 @@ class PrepSeg(ctypes.Structure):
     _fields_ = [("src", c_void_p), ("dst", c_void_p),
                 ("B_src", c_int), ("C", c_int), ("Hs", c_int), ("Ws", c_int), ("h", c_int), ("w", c_int),
                 ("y0", c_int), ("x0", c_int), ("prob", ctypes.c_float), ("keep", c_void_p)]
+
+
+class DataItem(ctypes.Structure):
+    """kdlae_data_item (include/kdlae.h): one source image and one destination slot of a kdlae_data_sample call."""
+
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("z", c_void_p), ("counts", c_void_p), ("mean", c_void_p),
+                ("std", c_void_p), ("sy", c_int64), ("sx", c_int64), ("sc", c_int64), ("count_n", c_int64),
+                ("count_thr", c_double), ("loc", c_double), ("scale", c_double), ("div", c_double),
+                ("src_u8", c_int), ("Hs", c_int), ("Ws", c_int), ("C", c_int),
+                ("Hc", c_int), ("Wc", c_int), ("Hp", c_int), ("Wp", c_int), ("pad_mode", c_int),
+                ("top", c_int), ("left", c_int), ("h", c_int), ("w", c_int),
+                ("dihedral", c_int), ("reverse_c", c_int), ("noise", c_int), ("reserved", c_int)]
 
 
 _lib = None
@@ -276,6 +289,11 @@ def lib() -> ctypes.CDLL:
     L.kdlae_train_mask_frames.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                           ctypes.POINTER(c_float), c_int, c_float, c_void_p, ctypes.c_uint64,
                                           ctypes.c_uint64, c_void_p]
+    L.kdlae_data_sample.argtypes = [ctypes.POINTER(DataItem), c_void_p, c_int, ctypes.c_uint64, ctypes.c_uint64,
+                                    c_void_p]
+    L.kdlae_data_count.argtypes = [c_void_p, c_int, c_int64, c_void_p, c_void_p]
+    L.kdlae_data_finish.argtypes = [c_void_p, c_int, c_int, c_int64, c_void_p, c_double, c_float, c_void_p, c_void_p,
+                                    c_void_p]
     L.kdlae_debug_tgemm.argtypes = [c_void_p, c_void_p]
     for f in ("kdlae_debug_gemm", "kdlae_debug_gram", "kdlae_debug_ln", "kdlae_debug_small_in",
               "kdlae_debug_train", "kdlae_debug_train_s", "kdlae_debug_infer"):

@@ -25,7 +25,7 @@ from . import _lib
 from ._lib import PrepSeg
 
 __all__ = ["ProgressiveSchedule", "ProgressiveBatcher", "train_prepare", "mask_frames", "interpolation_inputs",
-           "test1_inputs", "choice_threshold"]
+           "test1_inputs", "train_inputs", "choice_threshold"]
 
 
 def _vp(t):
@@ -251,7 +251,8 @@ def _frames_by_item(frames, item_probs, interpolate, rng, seed, call, value, per
     draw per (item, frame) in that order, as a single-worker loader running the dataset's ``__getitem__`` item after
     item draws them (a negative probability draws nothing: ``input_mask`` returns the frame unchanged).
     ``per_item`` False: every row is the same and the batch is one launch with ``call``.  ``per_item`` True: one
-    launch per item into its slice of the output, item b with ``call + b``, whatever the rows turn out to be."""
+    launch per item into its slice of the output, item b with ``call + b``, whatever the rows turn out to be;
+    ``interpolate`` may then be one flag per item."""
     if rng not in ("philox", "numpy"):
         raise ValueError(f"rng must be 'philox' or 'numpy', got {rng!r}")
     frames = _check(frames, "frames")
@@ -269,8 +270,8 @@ def _frames_by_item(frames, item_probs, interpolate, rng, seed, call, value, per
         return mask_frames(frames, rows[0], interpolate, keep, seed, call, value)
     out = torch.empty_like(frames)
     for b in range(B):
-        mask_frames(frames[b:b + 1], rows[b], interpolate, keep[b:b + 1] if keep is not None else None, seed, call + b,
-                    value, out=out[b:b + 1])
+        mask_frames(frames[b:b + 1], rows[b], interpolate[b] if isinstance(interpolate, (list, tuple)) else interpolate,
+                    keep[b:b + 1] if keep is not None else None, seed, call + b, value, out=out[b:b + 1])
     return out
 
 
@@ -293,6 +294,29 @@ def test1_inputs(frames, prob, rng="philox", seed=0, call=0, value=0.1):
     B, F = _check(frames, "frames").shape[:2]
     rows = [[prob + 0.6 if random.random() < 0.2 else prob for _ in range(F)] for _ in range(B)]
     return _frames_by_item(frames, rows, False, rng, seed, call, value, per_item=True)
+
+
+def _train_row(F, prob):
+    """One item's draws of the ``train`` phase: (per-frame probabilities, interpolate)."""
+    if random.random() < 0.64:
+        return [prob + 0.5 if random.random() > 0.64 else prob for _ in range(F)], False
+    return [prob + 0.5 if f % 2 == 1 else prob for f in range(F)], True
+
+
+def train_inputs(frames, prob, rng="philox", seed=0, call=0, value=0.1):
+    """Inputs of the dataset's ``train`` phase (paired_image_dataset.py:219-241), the rule KDLAES.yml trains with, for
+    ``frames`` [B, F, H, W]: per item one ``random.random() < 0.64`` draw on the host; when it holds, one
+    ``random.random() > 0.64`` per frame picks ``prob + 0.5`` instead of ``prob``; otherwise the item goes through
+    the interpolation rule (see ``interpolation_inputs``).  F must be odd: the reference asserts it in the
+    interpolation branch, which any item may take, and here it is checked before the first draw.  The draws come
+    in the reference's order, (item, frame); each item is a launch of its own, item b with ``call + b``."""
+    B, F = _check(frames, "frames").shape[:2]
+    if rng not in ("philox", "numpy"):
+        raise ValueError(f"rng must be 'philox' or 'numpy', got {rng!r}")
+    if F % 2 == 0:
+        raise ValueError(f"train_inputs: the interpolation branch needs an odd frame count, got {F}")
+    rows = [_train_row(F, prob) for _ in range(B)]
+    return _frames_by_item(frames, [r for r, _ in rows], [i for _, i in rows], rng, seed, call, value, per_item=True)
 
 
 test1_inputs.__test__ = False  # the name is the reference's phase; keep pytest from collecting it where imported

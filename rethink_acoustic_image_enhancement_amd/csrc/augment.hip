@@ -19,6 +19,7 @@
 
 #include <cstdint>
 
+#include "philox.h"
 #include "runtime.h"
 
 namespace kdlae {
@@ -62,18 +63,6 @@ struct FrameArgs {
   float fill;
   unsigned key0, key1, call_lo, call_hi;
 };
-
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-    c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c;
-}
 
 __device__ __forceinline__ bool philox_keep(unsigned word, float prob) {
   return (float)(word >> 8) * 0x1p-24f >= prob;
