@@ -529,6 +529,8 @@ int kdlae_data_finish(float* x, int B, int C, int64_t hw, const int32_t* counts,
 /* ---- Kernel self-test entry points (not part of the drop-in boundary; nothing here is on a forward
  * or training path).  tests/test_kernel_variants*_gpu.py: kdlae_debug_tgemm, kdlae_debug_gemm,
  * kdlae_debug_gram, kdlae_debug_ln, kdlae_debug_small_in, kdlae_debug_bn;
+ * tests/test_narrow_kernels_gpu.py: kdlae_debug_small_in (2-D, transposed), kdlae_debug_bn ops 6-9,
+ * kdlae_debug_head_train, kdlae_debug_train_s ops 6-7;
  * tests/test_train_kernels_gpu.py: kdlae_debug_train, kdlae_debug_train_s (the training steps'
  * non-GEMM kernels); tests/test_infer_kernels_gpu.py: kdlae_debug_infer (the forward paths' other kernels).
  * One launch of the training GEMM family on caller device buffers:
@@ -626,7 +628,10 @@ int kdlae_debug_ln(const kdlae_debug_ln_desc* d, void* stream);
 
 /* Small-input 3x3 / 3x3x3 conv (conv_small.hip), Cin * 9 * kt <= 36, Cout % 16 == 0: input element
  * (b, frame t, y, x, c) at in[b sb + t st + y sy + x sx + c sc] (minus in_sub at the same offset),
- * w [Cout][Cin][kt][3][3], NHWC output [Bn * F * H * W][ldo]; valid input extent vh x vw (0 = H, W). */
+ * w [Cout][Cin][kt][3][3], NHWC output [Bn * F * H * W][ldo] (16-byte aligned, ldo % 4 == 0); valid input
+ * extent vh x vw (0 = H, W).  wt > 0 (kt 1, wt >= Cout): the conv is the transpose (the input gradient) of a
+ * Cout' = Cin, Cin' = wt conv whose weight w is [Cin][wt][3][3]: out[p][n] = sum_{c, tap} in[p + off(tap)][c]
+ * w[c][n][8 - tap], n < Cout. */
 typedef struct kdlae_debug_small_in_desc {
   const float* in; int64_t sb, sc, sy, sx, st;
   const float* in_sub;
@@ -634,6 +639,7 @@ typedef struct kdlae_debug_small_in_desc {
   const float* w; const float* bias;
   float* out; int ldo;
   int Bn, H, W, vh, vw, relu;
+  int wt;
 } kdlae_debug_small_in_desc;
 int kdlae_debug_small_in(const kdlae_debug_small_in_desc* d, void* stream);
 
@@ -643,7 +649,12 @@ int kdlae_debug_small_in(const kdlae_debug_small_in_desc* d, void* stream);
  *   2 bn_bwd_reduce: (dy, y, x) -> dgamma, dbeta [C]
  *   3 bn_bwd_dx: out = gamma rstd (dy [y > 0] - dbeta / P - xhat dgamma / P)
  *   4 upsample2x_bwd: x = the [N][2h][2w] gradient -> out [N][h][w]       5 upsample2x: x [N][h][w] -> out
- * part: scratch of >= 2048 C floats (ops 0, 2). */
+ *   6 asdqe_pack_inputs: x = lq, y = gt, both NCHW [N][C = ci <= 4][h][w] -> out = xin [N Hp Wp][12] (16-byte
+ *     aligned): lq, gt, lq - gt at 4 channels each, zero past ci and past h x w; Hp >= h, Wp >= w
+ *   7 narrow_w_copy: x = src [N = Cout][4][9] -> out = dst [N][C = ci <= 4][9]
+ *   8 bcast_rows: x = N rows of C floats at row stride ldx -> out[(n P + p) ldo + c] = x[n ldx + c] scale, p < P
+ *   9 grad_commit: out[i] = (accumulate ? out[i] : 0) + x[i], i < P (P % 4 == 0, both 16-byte aligned)
+ * part: scratch of >= 2048 C floats (ops 0, 2).  A bad argument of ops 5-9 is KDLAE_EINVAL_* before any launch. */
 typedef struct kdlae_debug_bn_desc {
   int op;
   const float* x; int ldx;
@@ -657,8 +668,34 @@ typedef struct kdlae_debug_bn_desc {
   int C; int64_t P;
   int N, h, w;
   float* part; int64_t part_floats;
+  int Hp, Wp;       /* op 6 */
+  int accumulate;   /* op 9 */
+  float scale;      /* op 8 */
 } kdlae_debug_bn_desc;
 int kdlae_debug_bn(const kdlae_debug_bn_desc* d, void* stream);
+
+/* ASDQE train-mode regressor head (bn_train.hip; csrc/train_a.h HeadTrain), one image per block:
+ *   g = inv_hw sum_slots partial [B][slots][C]; f = wo g + bo [M]; a1 = w1 f + b1 [N1]; h1 = relu(a1) mask1;
+ *   a2 = w2 h1 + b2 [N2]; h2 = relu(a2) mask2; score = tanh(w3 . h2 + b3).  masks [B][N1] / [B][N2] or null.
+ * dir 0: forward -> score [B], save [B][2 (C + M + N1 + N2) + 4] (g, f, a1, a2, then the backward's rows).
+ * dir 1: backward from dscore [B] and the save of a dir 0 call with the same operands -> the eight gradients
+ *   (each a sum over the images) and, per image, dgap [C] at save row offset C + 2 (M + N1 + N2) + 4.
+ * C, M, N1, N2 <= 1024; save_floats >= B (2 (C + M + N1 + N2) + 4); a bad argument is KDLAE_EINVAL_* before
+ * any launch. */
+typedef struct kdlae_debug_head_train_desc {
+  int dir;
+  const float* partial; int slots, C; float inv_hw;
+  const float* wo; const float* bo; int M;
+  const float* w1; const float* b1; int N1;
+  const float* w2; const float* b2; int N2;
+  const float* w3; const float* b3;
+  const float* mask1; const float* mask2;
+  float* score; int B;
+  float* save; int64_t save_floats;
+  const float* dscore;
+  float* gwo; float* gbo; float* gw1; float* gb1; float* gw2; float* gb2; float* gw3; float* gb3;
+} kdlae_debug_head_train_desc;
+int kdlae_debug_head_train(const kdlae_debug_head_train_desc* d, void* stream);
 
 /* Non-GEMM kernels of the KDLAE-T training step (train.hip, train_dwg.hip, train_small.hip; launch
  * interface and operand meaning: csrc/train_kernels.h), one launch per call on caller buffers
@@ -716,7 +753,13 @@ int kdlae_debug_train_blocks(int which, int64_t n, int a, int b, int64_t cap);
  *   op 2 wperm         in0 [O][C][27] -> out [O][27][C] (dir 0) or back (dir 1)
  *   op 3 relu_mask     out = dy (in place) *= (in0 = y > 0)
  *   op 4 maxpool2_bwd  in0 = the pool's input [B, F, 2H, 2W], in1 = dout [B, F, H, W], in2 = dskip (or null) -> out = din
- *   op 5 upshuffle_add in0 = U [B, F, H/2, W/2] (4 C), in1 = skip [B, F, H, W], bias (or null) -> out = D */
+ *   op 5 upshuffle_add in0 = U [B, F, H/2, W/2] (4 C), in1 = skip [B, F, H, W], bias (or null) -> out = D
+ *   op 6 pack_conv     in0 = w [O = cout][C = cin][27], dir = dx -> out = fragment order [ntiles][kgroups][64][4],
+ *                      element (l, e) of (t, g) = Wm(16 t + l % 16, 16 g + 4 (l / 16) + e), k = tap in_pad + c;
+ *                      dx 0: Wm(o, k) = w[o][c][tap] (nout = cout, nin = cin); dx 1: Wm(c, tap in_pad + o) =
+ *                      w[o][c][26 - tap] (nout = cin, nin = cout); in_pad = nin rounded up to 16, ntiles =
+ *                      ceil(nout / 16), kgroups = 27 in_pad / 16; zero past nout and nin
+ *   op 7 relu          out = max(out, 0) in place over C of its ldo columns */
 typedef struct kdlae_debug_train_s_desc {
   int op;
   const float* in[3]; int ldi[3];

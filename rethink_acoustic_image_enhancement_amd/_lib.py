@@ -57,6 +57,7 @@ EXPORTS = (
     "kdlae_data_sample", "kdlae_data_count", "kdlae_data_finish",
     "kdlae_debug_train", "kdlae_debug_train_blocks", "kdlae_debug_train_s",
     "kdlae_debug_infer",
+    "kdlae_debug_head_train",
 )
 
 
@@ -126,6 +127,43 @@ class InferDesc(ctypes.Structure):
                 ("out_mode", c_int), ("nout", c_int), ("use_wp3", c_int),
                 ("out_nchw", c_int), ("wt", c_int), ("slots", c_int),
                 ("M", c_int), ("N1", c_int), ("N2", c_int)]
+
+
+class SmallInDesc(ctypes.Structure):
+    """kdlae_debug_small_in_desc (include/kdlae.h): the C field `in` is `inp` here."""
+
+    _fields_ = [("inp", c_void_p), ("sb", c_int64), ("sc", c_int64), ("sy", c_int64), ("sx", c_int64),
+                ("st", c_int64), ("in_sub", c_void_p),
+                ("Cin", c_int), ("Cout", c_int), ("dil", c_int), ("kt", c_int), ("F", c_int),
+                ("w", c_void_p), ("bias", c_void_p), ("out", c_void_p), ("ldo", c_int),
+                ("Bn", c_int), ("H", c_int), ("W", c_int), ("vh", c_int), ("vw", c_int), ("relu", c_int),
+                ("wt", c_int)]
+
+
+class BnDesc(ctypes.Structure):
+    """kdlae_debug_bn_desc (include/kdlae.h)."""
+
+    _fields_ = [("op", c_int), ("x", c_void_p), ("ldx", c_int), ("y", c_void_p), ("ldy", c_int),
+                ("dy", c_void_p), ("ldd", c_int), ("out", c_void_p), ("ldo", c_int),
+                ("mean", c_void_p), ("rstd", c_void_p), ("running_mean", c_void_p), ("running_var", c_void_p),
+                ("momentum", ctypes.c_float), ("gamma", c_void_p), ("beta", c_void_p), ("dgamma", c_void_p),
+                ("dbeta", c_void_p), ("C", c_int), ("P", c_int64), ("N", c_int), ("h", c_int), ("w", c_int),
+                ("part", c_void_p), ("part_floats", c_int64),
+                ("Hp", c_int), ("Wp", c_int), ("accumulate", c_int), ("scale", ctypes.c_float)]
+
+
+class HeadTrainDesc(ctypes.Structure):
+    """kdlae_debug_head_train_desc (include/kdlae.h)."""
+
+    _fields_ = [("dir", c_int), ("partial", c_void_p), ("slots", c_int), ("C", c_int), ("inv_hw", ctypes.c_float),
+                ("wo", c_void_p), ("bo", c_void_p), ("M", c_int),
+                ("w1", c_void_p), ("b1", c_void_p), ("N1", c_int),
+                ("w2", c_void_p), ("b2", c_void_p), ("N2", c_int),
+                ("w3", c_void_p), ("b3", c_void_p), ("mask1", c_void_p), ("mask2", c_void_p),
+                ("score", c_void_p), ("B", c_int), ("save", c_void_p), ("save_floats", c_int64),
+                ("dscore", c_void_p),
+                ("gwo", c_void_p), ("gbo", c_void_p), ("gw1", c_void_p), ("gb1", c_void_p),
+                ("gw2", c_void_p), ("gb2", c_void_p), ("gw3", c_void_p), ("gb3", c_void_p)]
 
 
 class PrepSeg(ctypes.Structure):
@@ -296,7 +334,7 @@ def lib() -> ctypes.CDLL:
                                     c_void_p]
     L.kdlae_debug_tgemm.argtypes = [c_void_p, c_void_p]
     for f in ("kdlae_debug_gemm", "kdlae_debug_gram", "kdlae_debug_ln", "kdlae_debug_small_in",
-              "kdlae_debug_train", "kdlae_debug_train_s", "kdlae_debug_infer"):
+              "kdlae_debug_train", "kdlae_debug_train_s", "kdlae_debug_infer", "kdlae_debug_head_train"):
         getattr(L, f).argtypes = [c_void_p, c_void_p]
     L.kdlae_debug_train_blocks.argtypes = [c_int, c_int64, c_int, c_int, c_int64]
     L.kdlae_debug_gemm_variant.argtypes = [c_int, c_int, ctypes.POINTER(c_int)]

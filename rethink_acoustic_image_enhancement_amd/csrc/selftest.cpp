@@ -7,12 +7,14 @@
 //   kdlae_debug_gram                       MDTA dwconv + Gram
 //   kdlae_debug_ln                         training LayerNorm forward / backward
 //   kdlae_debug_small_in                   small-input 3x3 / 3x3x3 conv
-//   kdlae_debug_bn                         ASDQE training BatchNorm / upsample kernels
+//   kdlae_debug_bn                         ASDQE training BatchNorm / upsample kernels and the step's small helpers
+//                                          (input packing, narrow weight copy, row broadcast, gradient commit)
+//   kdlae_debug_head_train                 ASDQE train-mode regressor head, forward and backward
 //   kdlae_debug_train, _train_blocks       the KDLAE-T step's non-GEMM kernels: MDTA softmax core and its
 //                                          backward, depthwise / gate family, small-side 3x3 weight gradient,
 //                                          column reductions, layout kernels (tests/test_train_kernels_gpu.py)
 //   kdlae_debug_train_s                    the KDLAE-S step's im2col / col2im, weight permute, ReLU mask,
-//                                          max-pool backward, transposed-conv scatter
+//                                          max-pool backward, transposed-conv scatter, fragment packing, ReLU
 //   kdlae_debug_infer                      the forward paths' kernels outside those families: fused GDFN tail,
 //                                          fused feed-forward half, fused MDTA pass 1, softmax + fold, dwconv
 //                                          gate, LDS-tiled convs, small-output conv, max-pool, ASDQE pool + head
@@ -219,6 +221,11 @@ extern "C" int kdlae_debug_small_in(const kdlae_debug_small_in_desc* d, void* st
   if (!d || !d->in || !d->w || !d->out) return fail(KDLAE_EINVAL_CONFIG, "null operand");
   if (d->Bn < 1 || d->H < 1 || d->W < 1 || d->Cin < 1 || d->Cout < 16 || d->ldo < d->Cout)
     return fail(KDLAE_EINVAL_SHAPE, "bad small-input conv geometry");
+  if ((d->kt != 1 && d->kt != 3) || d->Cin * 9 * d->kt > 36 || d->Cout % 16)
+    return fail(KDLAE_EINVAL_SHAPE, "small-input conv: kt 1 or 3, Cin * 9 * kt <= 36, Cout % 16 == 0");
+  if (d->ldo % 4 || !kdlae::al16(d->out)) return fail(KDLAE_EINVAL_SHAPE, "small-input conv: out 16-byte aligned, ldo % 4 == 0");
+  if (d->wt < 0 || (d->wt && (d->kt != 1 || d->wt < d->Cout)))
+    return fail(KDLAE_EINVAL_SHAPE, "small-input conv: wt needs kt 1 and wt >= Cout");
   kdlae::SmallInParams p{};
   p.in = d->in;
   p.sb = d->sb;
@@ -242,6 +249,7 @@ extern "C" int kdlae_debug_small_in(const kdlae_debug_small_in_desc* d, void* st
   p.vh = d->vh;
   p.vw = d->vw;
   p.relu = d->relu;
+  p.wt = d->wt;
   const hipError_t e = kdlae::launch_conv_small_in(p, (hipStream_t)stream);
   if (e != hipSuccess) return fail(KDLAE_EHIP, std::string("kdlae_debug_small_in: ") + hipGetErrorString(e));
   return KDLAE_OK;
@@ -276,9 +284,67 @@ extern "C" int kdlae_debug_bn(const kdlae_debug_bn_desc* d, void* stream) {
         return fail(KDLAE_EINVAL_SHAPE, "bad upsample geometry");
       e = kdlae::launch_upsample2x(d->x, d->ldx, d->out, d->ldo, d->C, d->N, d->h, d->w, s);
       break;
-    default: return fail(KDLAE_EINVAL_CONFIG, "op must be 0..5");
+    case 6:  // x = lq, y = gt [N][C = ci][h][w] -> out = xin [N Hp Wp][12]
+      if (!d->x || !d->y || !d->out) return fail(KDLAE_EINVAL_CONFIG, "null operand");
+      if (d->C < 1 || d->C > 4 || d->N < 1 || d->h < 1 || d->w < 1 || d->Hp < d->h || d->Wp < d->w ||
+          (long long)d->N * d->Hp * d->Wp * 12 >= (1LL << 31) || !kdlae::al16(d->out))
+        return fail(KDLAE_EINVAL_SHAPE, "asdqe_pack_inputs: ci 1..4, Hp >= h, Wp >= w, out 16-byte aligned");
+      e = tr::launch_asdqe_pack_inputs(d->x, d->y, d->C, d->N, d->h, d->w, d->Hp, d->Wp, d->out, s);
+      break;
+    case 7:  // x = src [N = Cout][4][9] -> out = dst [N][C = ci][9]
+      if (!d->x || !d->out) return fail(KDLAE_EINVAL_CONFIG, "null operand");
+      if (d->C < 1 || d->C > 4 || d->N < 1 || d->N > (1 << 20)) return fail(KDLAE_EINVAL_SHAPE, "narrow_w_copy: ci 1..4, Cout >= 1");
+      e = tr::launch_narrow_w_copy(d->x, d->out, d->N, d->C, s);
+      break;
+    case 8:  // x = v rows at stride ldx, N images of P pixels -> out [N P][ldo]
+      if (!d->x || !d->out) return fail(KDLAE_EINVAL_CONFIG, "null operand");
+      if (d->C < 4 || d->C % 4 || d->C > 1024 || d->N < 1 || d->P < 1 || d->ldx < d->C || d->ldx % 4 || d->ldo < d->C ||
+          d->ldo % 4 || !kdlae::al16(d->x) || !kdlae::al16(d->out) || (long long)d->N * d->P * d->ldo >= (1LL << 31))
+        return fail(KDLAE_EINVAL_SHAPE, "bcast_rows: C % 4 == 0, C <= 1024, ldx, ldo >= C and % 4 == 0, 16-byte aligned views");
+      e = tr::launch_bcast_rows(d->x, d->ldx, d->C, d->N, d->P, d->scale, d->out, d->ldo, s);
+      break;
+    case 9:  // x = g [P], out = grad [P]
+      if (!d->x || !d->out) return fail(KDLAE_EINVAL_CONFIG, "null operand");
+      if (d->P < 4 || d->P % 4 || !kdlae::al16(d->x) || !kdlae::al16(d->out))
+        return fail(KDLAE_EINVAL_SHAPE, "grad_commit: n >= 4, n % 4 == 0, 16-byte aligned operands");
+      e = tr::launch_grad_commit(d->x, d->out, d->P, d->accumulate ? 1 : 0, s);
+      break;
+    default: return fail(KDLAE_EINVAL_CONFIG, "op must be 0..9");
   }
   if (e != hipSuccess) return fail(KDLAE_EHIP, std::string("kdlae_debug_bn: ") + hipGetErrorString(e));
+  return KDLAE_OK;
+}
+
+extern "C" int kdlae_debug_head_train(const kdlae_debug_head_train_desc* d, void* stream) {
+  if (!d) return fail(KDLAE_EINVAL_CONFIG, "null descriptor");
+  if (d->dir != 0 && d->dir != 1) return fail(KDLAE_EINVAL_CONFIG, "dir must be 0 or 1");
+  if (!d->wo || !d->bo || !d->w1 || !d->b1 || !d->w2 || !d->b2 || !d->w3 || !d->b3 || !d->save)
+    return fail(KDLAE_EINVAL_CONFIG, "null operand");
+  auto dim_ok = [](int n) { return n >= 1 && n <= 1024; };
+  if (d->B < 1 || d->B > 65535 || !dim_ok(d->C) || !dim_ok(d->M) || !dim_ok(d->N1) || !dim_ok(d->N2))
+    return fail(KDLAE_EINVAL_SHAPE, "head: B >= 1, C, M, N1, N2 in 1..1024");
+  if (d->save_floats < (long long)d->B * tr::head_save_floats(d->C, d->M, d->N1, d->N2))
+    return fail(KDLAE_EINVAL_SHAPE, "save must hold B * head_save_floats floats");
+  tr::HeadTrain p{};
+  p.partial = d->partial; p.slots = d->slots; p.C = d->C; p.inv_hw = d->inv_hw;
+  p.wo = d->wo; p.bo = d->bo; p.M = d->M;
+  p.w1 = d->w1; p.b1 = d->b1; p.N1 = d->N1;
+  p.w2 = d->w2; p.b2 = d->b2; p.N2 = d->N2;
+  p.w3 = d->w3; p.b3 = d->b3;
+  p.mask1 = d->mask1; p.mask2 = d->mask2;
+  p.score = d->score; p.B = d->B; p.save = d->save;
+  hipError_t e;
+  if (d->dir == 0) {
+    if (!d->partial || !d->score) return fail(KDLAE_EINVAL_CONFIG, "null operand");
+    if (d->slots < 1 || d->slots > 65535) return fail(KDLAE_EINVAL_SHAPE, "head: slots >= 1");
+    e = tr::launch_head_train_fwd(p, (hipStream_t)stream);
+  } else {
+    if (!d->dscore || !d->gwo || !d->gbo || !d->gw1 || !d->gb1 || !d->gw2 || !d->gb2 || !d->gw3 || !d->gb3)
+      return fail(KDLAE_EINVAL_CONFIG, "null operand");
+    const tr::HeadTrainGrads g{d->gwo, d->gbo, d->gw1, d->gb1, d->gw2, d->gb2, d->gw3, d->gb3};
+    e = tr::launch_head_train_bwd(p, d->dscore, g, (hipStream_t)stream);
+  }
+  if (e != hipSuccess) return fail(KDLAE_EHIP, std::string("kdlae_debug_head_train: ") + hipGetErrorString(e));
   return KDLAE_OK;
 }
 
@@ -478,6 +544,13 @@ extern "C" int kdlae_debug_train_s(const kdlae_debug_train_s_desc* d, void* stre
     if (e != hipSuccess) return fail(KDLAE_EHIP, std::string("kdlae_debug_train_s: ") + hipGetErrorString(e));
     return KDLAE_OK;
   }
+  if (d->op == 6) {  // in0 = w [O = cout][C = cin][27], dir = dx -> out: ceil(nout / 16) * 27 in_pad / 16 * 256 floats
+    if (!d->in[0] || !d->out) return fail(KDLAE_EINVAL_CONFIG, "null operand");
+    if (d->O < 1 || d->O > 4096 || C < 1 || C > 4096 || (d->dir != 0 && d->dir != 1)) return fail(KDLAE_EINVAL_SHAPE, bad);
+    const hipError_t e = tr::launch_pack_conv(d->in[0], d->O, C, d->dir, d->out, s);
+    if (e != hipSuccess) return fail(KDLAE_EHIP, std::string("kdlae_debug_train_s: ") + hipGetErrorString(e));
+    return KDLAE_OK;
+  }
   if (d->B < 1 || d->F < 1 || d->H < 1 || d->W < 1 || C < 1 || C > (1 << 16) ||
       (long long)d->B * d->F * d->H * d->W * 27 * C >= kMaxIdx)
     return fail(KDLAE_EINVAL_SHAPE, bad);
@@ -511,7 +584,11 @@ extern "C" int kdlae_debug_train_s(const kdlae_debug_train_s_desc* d, void* stre
       e = tr::launch_upshuffle_add(d->in[0], d->ldi[0], d->bias, d->in[1], d->ldi[1], d->out, d->ldo, C, d->B, d->F, d->H,
                                    d->W, s);
       break;
-    default: return fail(KDLAE_EINVAL_CONFIG, "op must be 0..5");
+    case 7:  // in place on out
+      if (!view_ok(d->out, d->ldo, C, px)) return fail(KDLAE_EINVAL_SHAPE, bad);
+      e = tr::launch_relu(d->out, d->ldo, C, px, s);
+      break;
+    default: return fail(KDLAE_EINVAL_CONFIG, "op must be 0..7");
   }
   if (e != hipSuccess) return fail(KDLAE_EHIP, std::string("kdlae_debug_train_s: ") + hipGetErrorString(e));
   return KDLAE_OK;

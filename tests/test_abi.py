@@ -338,3 +338,81 @@ def test_debug_infer_entry_refuses_bad_arguments():
     assert f(**hd, scratch_floats=2 * 7 * 64 - 1, **geo) == 1 and f(**{**hd, "N1": 1025}, scratch_floats=1 << 20, **geo) == 1
     assert f(**{**hd, "slots": 0}, scratch_floats=1 << 20, **geo) == 1
     assert f(**{**hd, "bias": [P, P, P, None]}, scratch_floats=1 << 20, **geo) == 2
+
+
+# ------------------------------------------------------------------ narrow-kernel self-test entries
+def test_debug_narrow_entries_refuse_bad_arguments():
+    """kdlae_debug_small_in, kdlae_debug_bn ops 6-9, kdlae_debug_head_train and kdlae_debug_train_s ops 6-7
+    check every launcher precondition before they launch (1 = EINVAL_SHAPE, 2 = EINVAL_CONFIG).  The
+    pointers here are never dereferenced."""
+    from rethink_acoustic_image_enhancement_amd._lib import BnDesc, HeadTrainDesc, SmallInDesc, TrainSDesc
+
+    L = _lib.lib()
+    P = 0x1000  # a non-null, 16-byte aligned "device pointer"
+
+    def call(fn, cls, **kw):
+        d = cls()
+        for k, v in kw.items():
+            if isinstance(v, list):
+                for i, x in enumerate(v):
+                    getattr(d, k)[i] = x
+            else:
+                setattr(d, k, v)
+        return getattr(L, fn)(ctypes.byref(d), None)
+
+    # small-in: null operands, ci > 4, Cout % 16, kt, the float4 output view, wt < Cout, wt with kt 3
+    si = dict(inp=P, w=P, out=P, sb=63, sc=1, sy=9, sx=1, Cin=3, Cout=48, dil=1, kt=1, F=1, ldo=52, Bn=2, H=7, W=9)
+    sm = lambda **kw: call("kdlae_debug_small_in", SmallInDesc, **{**si, **kw})
+    assert L.kdlae_debug_small_in(None, None) == 2
+    assert sm(inp=None) == 2 and sm(w=None) == 2 and sm(out=None) == 2
+    assert sm(Cin=5) == 1 and sm(Cin=2, kt=3) == 1 and sm(Cout=40, ldo=44) == 1 and sm(kt=2) == 1
+    assert sm(ldo=50) == 1 and sm(out=P + 4) == 1 and sm(ldo=44) == 1 and sm(H=0) == 1
+    assert sm(wt=47) == 1 and "wt" in _lib.last_error() and sm(wt=-1) == 1
+    assert sm(Cin=1, kt=3, F=2, wt=48) == 1
+    # kdlae_debug_bn ops 6-9
+    bn = lambda **kw: call("kdlae_debug_bn", BnDesc, **kw)
+    assert bn(op=10) == 2
+    pk = dict(op=6, x=P, y=P, out=P, C=3, N=2, h=5, w=7, Hp=8, Wp=8)
+    assert bn(**{**pk, "x": None}) == 2 and bn(**{**pk, "y": None}) == 2 and bn(**{**pk, "out": None}) == 2
+    assert bn(**{**pk, "C": 5}) == 1 and bn(**{**pk, "C": 0}) == 1 and bn(**{**pk, "Hp": 4}) == 1
+    assert bn(**{**pk, "Wp": 6}) == 1 and bn(**{**pk, "out": P + 4}) == 1 and bn(**{**pk, "N": 0}) == 1
+    nw = dict(op=7, x=P, out=P, C=3, N=16)
+    assert bn(**{**nw, "x": None}) == 2 and bn(**{**nw, "out": None}) == 2
+    assert bn(**{**nw, "C": 5}) == 1 and bn(**{**nw, "N": 0}) == 1
+    bc = dict(op=8, x=P, ldx=8, out=P, ldo=8, C=8, N=2, P=35, scale=1.0)
+    assert bn(**{**bc, "x": None}) == 2 and bn(**{**bc, "out": None}) == 2
+    assert bn(**{**bc, "C": 6}) == 1 and bn(**{**bc, "C": 1028, "ldx": 1028, "ldo": 1028}) == 1
+    assert bn(**{**bc, "ldx": 4}) == 1 and bn(**{**bc, "ldx": 10}) == 1 and bn(**{**bc, "ldo": 4}) == 1
+    assert bn(**{**bc, "ldo": 10}) == 1 and bn(**{**bc, "x": P + 4}) == 1 and bn(**{**bc, "out": P + 8}) == 1
+    assert bn(**{**bc, "P": 0}) == 1 and bn(**{**bc, "N": 0}) == 1
+    gc = dict(op=9, x=P, out=P, P=8)
+    assert bn(**{**gc, "x": None}) == 2 and bn(**{**gc, "out": None}) == 2
+    assert bn(**{**gc, "P": 6}) == 1 and "n % 4" in _lib.last_error() and bn(**{**gc, "P": 0}) == 1
+    assert bn(**{**gc, "x": P + 4}) == 1 and bn(**{**gc, "out": P + 8}) == 1
+    # head: null operands per direction, a dimension above 1024, save too small, slots
+    row = 2 * (64 + 48 + 256 + 64) + 4
+    ptrs = ("wo", "bo", "w1", "b1", "w2", "b2", "w3", "b3", "save")
+    gr = ("gwo", "gbo", "gw1", "gb1", "gw2", "gb2", "gw3", "gb3")
+    hd = dict(dir=0, partial=P, slots=5, C=64, inv_hw=1.0, M=48, N1=256, N2=64, score=P, B=3, save_floats=3 * row,
+              **{k: P for k in ptrs})
+    hb = dict(hd, dir=1, dscore=P, **{k: P for k in gr})
+    ht = lambda **kw: call("kdlae_debug_head_train", HeadTrainDesc, **kw)
+    assert L.kdlae_debug_head_train(None, None) == 2 and ht(**{**hd, "dir": 2}) == 2
+    for k in ptrs + ("partial", "score"):
+        assert ht(**{**hd, k: None}) == 2, k
+    for k in ptrs + gr + ("dscore",):
+        assert ht(**{**hb, k: None}) == 2, k
+    for k in ("C", "M", "N1", "N2"):
+        assert ht(**{**hd, k: 1025, "save_floats": 1 << 30}) == 1 and ht(**{**hb, k: 0}) == 1, k
+    assert ht(**{**hd, "save_floats": 3 * row - 1}) == 1 and "save" in _lib.last_error()
+    assert ht(**{**hb, "save_floats": 3 * row - 1}) == 1
+    assert ht(**{**hd, "slots": 0}) == 1 and ht(**{**hd, "B": 0}) == 1
+    # KDLAE-S pack_conv and relu
+    ts = lambda **kw: call("kdlae_debug_train_s", TrainSDesc, **kw)
+    assert ts(op=8, B=1, F=1, H=2, W=2, C=4) == 2
+    assert ts(op=6, inp=[None], out=P, C=16, O=16) == 2 and ts(op=6, inp=[P], out=None, C=16, O=16) == 2
+    assert ts(op=6, inp=[P], out=P, C=0, O=16) == 1 and ts(op=6, inp=[P], out=P, C=16, O=0) == 1
+    assert ts(op=6, inp=[P], out=P, C=16, O=16, dir=2) == 1
+    sg = dict(B=1, F=1, H=4, W=4)
+    assert ts(op=7, out=None, ldo=8, C=8, **sg) == 1 and ts(op=7, out=P, ldo=7, C=8, **sg) == 1
+    assert ts(op=7, out=P, ldo=8, C=8, B=1, F=1, H=0, W=4) == 1

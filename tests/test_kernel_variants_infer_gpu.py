@@ -65,7 +65,8 @@ class SmallInDesc(ctypes.Structure):
                 ("st", c_int64), ("in_sub", c_void_p),
                 ("Cin", c_int), ("Cout", c_int), ("dil", c_int), ("kt", c_int), ("F", c_int),
                 ("w", c_void_p), ("bias", c_void_p), ("out", c_void_p), ("ldo", c_int),
-                ("Bn", c_int), ("H", c_int), ("W", c_int), ("vh", c_int), ("vw", c_int), ("relu", c_int)]
+                ("Bn", c_int), ("H", c_int), ("W", c_int), ("vh", c_int), ("vw", c_int), ("relu", c_int),
+                ("wt", c_int)]
 
 
 def _ptr(t):
