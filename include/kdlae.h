@@ -442,6 +442,35 @@ int kdlae_metric_ssim(const float* pred, const float* gt, int B, int C, int Hs, 
                       int h, int w, int crop_border, int mode, int variant,
                       double* out, void* scratch, void* stream);
 
+/* ---- NIQE (niqe.hip).  The no-reference metric of Train/basicsr/metrics/niqe.py:10-205, up to the per-block
+ * moments its AGGD fits need, over the geometry and with the `mode` of the two entries above: the top-left h x w
+ * window of the stored x [B, C, Hs, Ws] minus crop_border on the four sides, then the largest multiple of 96 on
+ * each axis (H' x W'; nbh = H' / 96, nbw = W' / 96 blocks).  Values are on the 0..255 scale: mode 0 takes the floats
+ * as they are, mode 1 quantises as tensor2img does.  C = 3 is RGB and becomes the Y of MATLAB's YCbCr in the
+ * reference's operation order (/ 255 in fp32; 24.966 B + 128.553 G + 65.481 R + 16 in fp64, each product and sum
+ * rounded, / 255; to fp32; * 255); C = 1 takes the same / 255, * 255 in fp32.  convert: 0 ('y') only.
+ *   MSCN field f = (x - mu) / (sqrt|E[x^2] - mu^2| + 1): mu and E over window49 (host pointer, 7 x 7 doubles,
+ *   row-major, the `gaussian_window` of niqe_pris_params.npz) the way scipy.ndimage.convolve(mode='nearest')
+ *   forms them: the flipped window in row-major order, an fp64 multiply and an fp64 add per tap (nothing fused),
+ *   one rounding to fp32, indices clamped to the edge of the H' x W' image (never to stored pixels beyond it,
+ *   which are not read).  The rest is correctly rounded fp32.  Scale 2 repeats this on the 2 x 2 mean of the
+ *   image (((a + b) / 2 + (c + d) / 2) / 2 of the / 255 values, * 255, each step rounded in fp32; it stands for
+ *   cv2.resize(.., INTER_LINEAR) at one half) with 48 x 48 blocks.
+ *   Per block five maps: f and the fp32 products f * roll(f, s) for s = (0,1), (1,0), (1,1), (1,-1), the roll
+ *   wrapping inside the block.
+ * out [B][2 scales][nbw * nbh blocks][5 maps][5] (device, fp64), blocks in the reference's order (index
+ * bx * nbh + by): n_neg, n_pos, sum of x^2 over x < 0, sum of x^2 over x > 0, sum of |x|; zeros are on neither
+ * side.  fp64 sums in a fixed order without atomics: equal inputs give equal bits.
+ * field_s1 [B][H'][W'] / field_s2 [B][H'/2][W'/2] (device, may be NULL): the two fields, for tests.
+ * scratch: device buffer of at least kdlae_metric_niqe_scratch_bytes(B, h, w) bytes (4-byte aligned), its size in
+ * scratch_bytes.  Nothing synchronises.  Errors are found before any launch: C not 1 or 3, crop_border leaving
+ * no pixel, fewer than 96 pixels left on an axis, a window outside the storage, scratch too small:
+ * KDLAE_EINVAL_SHAPE; null pointers, mode or convert out of range: KDLAE_EINVAL_CONFIG. */
+int64_t kdlae_metric_niqe_scratch_bytes(int B, int h, int w);
+int kdlae_metric_niqe(const float* x, int B, int C, int Hs, int Ws, int h, int w, int crop_border, int mode,
+                      int convert, const double* window49, double* out, float* field_s1, float* field_s2,
+                      void* scratch, int64_t scratch_bytes, void* stream);
+
 /* ---- Progressive-learning batch preparation (augment.hip).  Replaces the host loop between the data loader and
  * feed_train_data (Train/basicsr/train.py:374-448): the stage's sub-batch (random.sample), one crop window for
  * the whole batch, and the Bernoulli input mask of paired_image_dataset.py:19-36 (a kept pixel comes back bit

@@ -53,6 +53,7 @@ EXPORTS = (
     "kdlae_debug_bn",
     "kdlae_metric_scratch_bytes", "kdlae_metric_psnr",
     "kdlae_metric_ssim_scratch_bytes", "kdlae_metric_ssim",
+    "kdlae_metric_niqe_scratch_bytes", "kdlae_metric_niqe",
     "kdlae_train_prepare", "kdlae_train_mask_frames",
     "kdlae_data_sample", "kdlae_data_count", "kdlae_data_finish",
     "kdlae_debug_train", "kdlae_debug_train_blocks", "kdlae_debug_train_s",
@@ -322,6 +323,11 @@ def lib() -> ctypes.CDLL:
     L.kdlae_metric_ssim_scratch_bytes.restype = c_int64
     L.kdlae_metric_ssim.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                     c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    L.kdlae_metric_niqe_scratch_bytes.argtypes = [c_int, c_int, c_int]
+    L.kdlae_metric_niqe_scratch_bytes.restype = c_int64
+    L.kdlae_metric_niqe.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                    ctypes.POINTER(ctypes.c_double), c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_int64, c_void_p]
     L.kdlae_train_prepare.argtypes = [ctypes.POINTER(PrepSeg), c_int, c_void_p, c_int, c_float, ctypes.c_uint64,
                                       ctypes.c_uint64, c_void_p]
     L.kdlae_train_mask_frames.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int,

@@ -265,4 +265,12 @@ struct ConvLdsParams {
 bool conv_lds_supported(int kt, int ntiles, int cin_pad);
 hipError_t launch_conv_lds(const ConvLdsParams& p, hipStream_t s);
 
+// NIQE (niqe.hip): the block side at scale 1 (scale 2 uses half of it) and the 7 x 7 window of the MSCN filter,
+// handed to the kernel by value in the order scipy's convolve walks it (the caller's window reversed).
+constexpr int kNiqeBlock = 96;
+constexpr int kNiqeTaps = 7;
+struct NiqeWindow {
+  double w[kNiqeTaps * kNiqeTaps];
+};
+
 }  // namespace kdlae

@@ -594,14 +594,19 @@ class KDLAESTrainer(_TrainingState):
         return self._opt_scratch[2048]
 
     @torch.no_grad()
-    def validate(self, batches, window_size=8, crop_border=0, use_image=False, metrics=("psnr",)):
+    def validate(self, batches, window_size=8, crop_border=0, use_image=False, metrics=("psnr",), niqe=False,
+                 niqe_params=None):
         """ImageCleanModel.nondist_validation (image_restoration_model.py:264-348) for ``(lq, gt)`` pairs of
         [B, F, H, W] tensors: reflect-pad to the multiple the student needs (2^levels, and ``window_size``),
         the inference engine, PSNR of the top-left H x W window against ``gt``.  Returns ``{'psnr': mean}``
         over all images; with ``"ssim"`` in ``metrics`` also ``{'ssim': mean}`` (``calculate_ssim`` over the
-        same window, 1 <= F <= 4 frames).  The trainer's state is untouched."""
-        from .metrics import psnr_batch, ssim_batch
+        same window, 1 <= F <= 4 frames).  ``niqe=True`` adds ``{'niqe': mean}``: ``calculate_niqe`` of the
+        output's window (F = 1 or 3; at least 96 x 96 pixels after ``crop_border``), always on ``tensor2img``'s
+        uint8 image, which is what the reference's function takes; ``niqe_params`` is the reference's pristine
+        model (``metrics.load_niqe_params``).  The trainer's state is untouched."""
+        from .metrics import load_niqe_params, niqe_batch, psnr_batch, ssim_batch
         want_psnr, want_ssim = _val_metrics(metrics)
+        niqe_p, niqes = (load_niqe_params(niqe_params) if niqe else None), []
         need = 1 << self.model.num_levels
         mult = math.lcm(need, int(window_size)) if window_size else need
         flat = _inference_flat(self, self.theta)
@@ -617,6 +622,8 @@ class KDLAESTrainer(_TrainingState):
                 vals.append(psnr_batch(out, gt.to(out.device), (h, w), crop_border, use_image))
             if want_ssim:
                 ssims.append(ssim_batch(out, gt.to(out.device), (h, w), crop_border, use_image))
+            if niqe:
+                niqes.append(niqe_batch(out, (h, w), crop_border, True, "y", niqe_p))
         if not seen:
             raise ValueError("validate: no batches")
         res = {}
@@ -624,6 +631,8 @@ class KDLAESTrainer(_TrainingState):
             res["psnr"] = float(torch.cat(vals).mean())
         if want_ssim:
             res["ssim"] = float(torch.cat(ssims).mean())
+        if niqe:
+            res["niqe"] = float(torch.cat(niqes).mean())
         return res
 
 
@@ -1183,7 +1192,8 @@ class KDLAETrainer(_TrainingState):
                 self.theta_ema[off:off + n].copy_(sd[k].detach().reshape(-1))
 
     @torch.no_grad()
-    def validate(self, batches, window_size=8, crop_border=0, use_image=False, use_ema=None, metrics=("psnr",)):
+    def validate(self, batches, window_size=8, crop_border=0, use_image=False, use_ema=None, metrics=("psnr",),
+                 niqe=False, niqe_params=None):
         """ImageCleanModel.nondist_validation with pad_test (image_restoration_model.py:226-348) over
         ``(lq, gt)`` pairs, ``lq = {'img', 'denoise_rate'}``, ``gt = {'hq', 'sr'}``: reflect-pad ``img`` and the
         rate map right and bottom to a multiple of ``window_size``, run the inference engine
@@ -1191,13 +1201,17 @@ class KDLAETrainer(_TrainingState):
         against its target.  Returns ``{'psnr_hq': mean, 'psnr_sr': mean}`` over all images (``psnr_sr`` only
         when ``static == 'train'``).  ``metrics``: ``"psnr"`` and / or ``"ssim"`` (the val.metrics names
         calculate_psnr / calculate_ssim, :324-336); with ``"ssim"`` the result also holds ``ssim_hq`` / ``ssim_sr``
-        over the same windows.
+        over the same windows.  ``niqe=True`` adds ``niqe_hq`` / ``niqe_sr``: ``calculate_niqe`` (the third
+        val.metrics type, no target needed) of the outputs' windows, always on ``tensor2img``'s uint8 image,
+        which is what the reference's function takes (at least 96 x 96 pixels after ``crop_border``);
+        ``niqe_params`` is the reference's pristine model (``metrics.load_niqe_params``).
 
         ``use_ema=None``: the EMA weights when ``ema_decay > 0`` (net_g_ema, :242-248), else the live ones.
         The chosen flat vector is packed straight into the module's inference handle; the trainer's buffers,
         the training engine and the module's parameters are not written, so training continues bit for bit."""
-        from .metrics import psnr_batch, ssim_batch
+        from .metrics import load_niqe_params, niqe_batch, psnr_batch, ssim_batch
         want_psnr, want_ssim = _val_metrics(metrics)
+        niqe_p, n_hqs, n_srs = (load_niqe_params(niqe_params) if niqe else None), [], []
         if use_ema is None:
             use_ema = self.theta_ema is not None
         if use_ema and self.theta_ema is None:
@@ -1224,10 +1238,15 @@ class KDLAETrainer(_TrainingState):
                 a_hq.append(fn(out["hq"], gt["hq"].to(img.device), (h, w), crop_border, use_image))
                 if out["sr"] is not None:
                     a_sr.append(fn(out["sr"], gt["sr"].to(img.device), (2 * h, 2 * w), crop_border, use_image))
+            if niqe:
+                n_hqs.append(niqe_batch(out["hq"], (h, w), crop_border, True, "y", niqe_p))
+                if out["sr"] is not None:
+                    n_srs.append(niqe_batch(out["sr"], (2 * h, 2 * w), crop_border, True, "y", niqe_p))
         if not seen:
             raise ValueError("validate: no batches")
         res = {}
-        for name, vals in (("psnr_hq", hqs), ("psnr_sr", srs), ("ssim_hq", s_hqs), ("ssim_sr", s_srs)):
+        for name, vals in (("psnr_hq", hqs), ("psnr_sr", srs), ("ssim_hq", s_hqs), ("ssim_sr", s_srs),
+                           ("niqe_hq", n_hqs), ("niqe_sr", n_srs)):
             if vals:
                 res[name] = float(torch.cat(vals).mean())
         return res
