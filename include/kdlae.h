@@ -559,7 +559,8 @@ int kdlae_data_finish(float* x, int B, int C, int64_t hw, const int32_t* counts,
  * or training path).  tests/test_kernel_variants*_gpu.py: kdlae_debug_tgemm, kdlae_debug_gemm,
  * kdlae_debug_gram, kdlae_debug_ln, kdlae_debug_small_in, kdlae_debug_bn;
  * tests/test_narrow_kernels_gpu.py: kdlae_debug_small_in (2-D, transposed), kdlae_debug_bn ops 6-9,
- * kdlae_debug_head_train, kdlae_debug_train_s ops 6-7;
+ * kdlae_debug_head_train, kdlae_debug_train_s ops 6-7; tests/test_bn_kernels_gpu.py: kdlae_debug_bn ops 0-5 (the
+ * batch-statistics BatchNorm kernels and the bilinear x2 pair, float64 with counted bounds);
  * tests/test_train_kernels_gpu.py: kdlae_debug_train, kdlae_debug_train_s (the training steps'
  * non-GEMM kernels); tests/test_infer_kernels_gpu.py: kdlae_debug_infer (the forward paths' other kernels).
  * One launch of the training GEMM family on caller device buffers:
@@ -683,7 +684,9 @@ int kdlae_debug_small_in(const kdlae_debug_small_in_desc* d, void* stream);
  *   7 narrow_w_copy: x = src [N = Cout][4][9] -> out = dst [N][C = ci <= 4][9]
  *   8 bcast_rows: x = N rows of C floats at row stride ldx -> out[(n P + p) ldo + c] = x[n ldx + c] scale, p < P
  *   9 grad_commit: out[i] = (accumulate ? out[i] : 0) + x[i], i < P (P % 4 == 0, both 16-byte aligned)
- * part: scratch of >= 2048 C floats (ops 0, 2).  A bad argument of ops 5-9 is KDLAE_EINVAL_* before any launch. */
+ * part: scratch of >= 2048 C floats (ops 0, 2).  A bad argument of ops 5-9 is KDLAE_EINVAL_* before any launch (op 5:
+ * C >= 4, C % 4 == 0, ldx, ldo >= C and % 4 == 0, 16-byte aligned views); ops 0-4 are refused by the launchers' own
+ * check, KDLAE_EHIP "invalid argument", before any launch as well. */
 typedef struct kdlae_debug_bn_desc {
   int op;
   const float* x; int ldx;

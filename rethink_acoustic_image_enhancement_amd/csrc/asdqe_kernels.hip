@@ -24,7 +24,14 @@ __global__ __launch_bounds__(256) void upsample2x_kernel(const float* __restrict
     r /= W2;
     const int oy = (int)(r % H2);
     const long long n = r / H2;
-    const float sy = rh * (float)oy, sx = rw * (float)ox;
+    // the products round on their own (no contraction into the subtractions below), so that upsample2x_bwd
+    // and the tests' reference form these weights bit for bit
+    float sy, sx;
+    {
+#pragma clang fp contract(off)
+      sy = rh * (float)oy;
+      sx = rw * (float)ox;
+    }
     const int y0 = (int)sy, x0 = (int)sx;
     const int yp = y0 < h - 1 ? 1 : 0, xp = x0 < w - 1 ? 1 : 0;
     const float ly1 = sy - (float)y0, ly0 = 1.f - ly1;

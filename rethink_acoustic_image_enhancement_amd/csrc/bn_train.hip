@@ -258,13 +258,21 @@ __global__ __launch_bounds__(kT) void upsample2x_bwd_kernel(const float* __restr
       wy[k] = 0.f;
       wx[k] = 0.f;
       if (oy >= 0 && oy < H2) {
-        const float sy = rh * (float)oy;
+        float sy;
+        {
+#pragma clang fp contract(off)
+          sy = rh * (float)oy;  // rounded on its own, as upsample2x_kernel does
+        }
         const int y0 = (int)sy, yp = y0 < h - 1 ? 1 : 0;
         const float l1 = sy - (float)y0, l0 = 1.f - l1;
         wy[k] = (y0 == iy ? l0 : 0.f) + (y0 + yp == iy ? l1 : 0.f);
       }
       if (ox >= 0 && ox < W2) {
-        const float sx = rw * (float)ox;
+        float sx;
+        {
+#pragma clang fp contract(off)
+          sx = rw * (float)ox;
+        }
         const int x0 = (int)sx, xp = x0 < w - 1 ? 1 : 0;
         const float l1 = sx - (float)x0, l0 = 1.f - l1;
         wx[k] = (x0 == ix ? l0 : 0.f) + (x0 + xp == ix ? l1 : 0.f);

@@ -282,6 +282,8 @@ extern "C" int kdlae_debug_bn(const kdlae_debug_bn_desc* d, void* stream) {
     case 5:
       if (!d->x || !d->out || d->N < 1 || d->h < 1 || d->w < 1 || d->ldx < d->C || d->ldo < d->C)
         return fail(KDLAE_EINVAL_SHAPE, "bad upsample geometry");
+      if (d->C < 4 || d->C % 4 || d->ldx % 4 || d->ldo % 4 || !kdlae::al16(d->x) || !kdlae::al16(d->out))
+        return fail(KDLAE_EINVAL_SHAPE, "upsample2x: C >= 4, C % 4 == 0, ldx, ldo % 4 == 0, 16-byte aligned views");
       e = kdlae::launch_upsample2x(d->x, d->ldx, d->out, d->ldo, d->C, d->N, d->h, d->w, s);
       break;
     case 6:  // x = lq, y = gt [N][C = ci][h][w] -> out = xin [N Hp Wp][12]
