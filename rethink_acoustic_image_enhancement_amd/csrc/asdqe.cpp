@@ -16,17 +16,12 @@
 #include <string>
 #include <vector>
 
-#include "param_layout.h"
 #include "runtime.h"
 
 using namespace kdlae;
 
-struct asdqe_handle {
+struct asdqe_handle : HandleBase {
   asdqe_config cfg{};
-  int device = 0;
-  ParamStore ps;
-  bool built = false, committed = false;
-  DeviceWeights dw;        // packed arena + the pack program that fills it from the parameters
   SmallW ext1[3];
   Gemm ext2[3];
   Gemm inc[2], dn[3][2], upc[3][2];
@@ -103,10 +98,7 @@ int asdqe_create(const asdqe_config* cfg, int device, asdqe_handle** out) {
 
 int asdqe_destroy(asdqe_handle* h) {
   if (!h) return KDLAE_OK;
-  {
-    DeviceGuard g(h->device);
-    h->dw.release();
-  }
+  handle_release(h);
   delete h;
   return KDLAE_OK;
 }
@@ -114,24 +106,20 @@ int asdqe_destroy(asdqe_handle* h) {
 int asdqe_num_params(const asdqe_handle* h) { return h ? (int)h->ps.lay.size() : 0; }
 
 int asdqe_param_info(const asdqe_handle* h, int index, const char** name, int64_t* numel) {
-  if (!h) return fail(KDLAE_ESTATE, "null handle");
-  return h->ps.lay.info(index, name, numel, nullptr);
+  return handle_param_info(h, index, name, numel);
 }
 
 int64_t asdqe_params_numel(const asdqe_handle* h) { return h ? h->ps.lay.total : -1; }
 
 int asdqe_set_param(asdqe_handle* h, const char* name, const float* host_data, int64_t numel) {
-  if (!h || !name || !host_data) return fail(KDLAE_ESTATE, "null argument");
-  return h->ps.set(name, host_data, numel);
+  return handle_set_param(h, name, host_data, numel);
 }
 
 }  // extern "C"
 
-// Records the packed layout (pack program, runtime.h) of this configuration once per handle.
-static int build_program_a(asdqe_handle* h) {
-  if (h->built) return KDLAE_OK;
-  PackProgram ar;
-  ar.nsrc = h->ps.lay.total;
+// Records the packed layout (pack program, runtime.h) of this configuration.
+static int record_program_a(HandleBase* base, PackProgram& ar) {
+  auto* h = static_cast<asdqe_handle*>(base);
   int err = KDLAE_OK;
   // BatchNorm2d eval (eps 1e-5) folded into the preceding conv: W' = s W, b' = s (b - rm) + beta,
   // s = gamma / sqrt(rv + eps): s and b' are derived values computed on the device before the gathers
@@ -246,43 +234,17 @@ static int build_program_a(asdqe_handle* h) {
   h->b2 = raw("regressor.5.bias", 64);
   h->w3 = raw("regressor.8.weight", 64);
   h->b3 = raw("regressor.8.bias", 1);
-  if (err) return err;
-  DeviceGuard dg(h->device);
-  int rc = h->dw.upload_program(ar);
-  if (rc) return rc;
-  h->built = true;
-  return KDLAE_OK;
+  return err;
 }
 
 extern "C" {
 
-int asdqe_commit_params(asdqe_handle* h, void* stream) {
-  if (!h) return fail(KDLAE_ESTATE, "null handle");
-  int rc = h->ps.check_complete();
-  if (rc) return rc;
-  if ((rc = build_program_a(h))) return rc;
-  DeviceGuard g(h->device);
-  if ((rc = h->dw.run_host(h->ps.flat(), reinterpret_cast<hipStream_t>(stream)))) return rc;
-  h->committed = true;
-  return KDLAE_OK;
-}
+int asdqe_commit_params(asdqe_handle* h, void* stream) { return handle_commit(h, record_program_a, stream); }
 
-int asdqe_prepare(asdqe_handle* h) {
-  if (!h) return fail(KDLAE_ESTATE, "null handle");
-  return build_program_a(h);
-}
+int asdqe_prepare(asdqe_handle* h) { return handle_prepare(h, record_program_a); }
 
 int asdqe_pack_device(asdqe_handle* h, const float* params, int64_t numel, void* stream) {
-  if (!h) return fail(KDLAE_ESTATE, "null handle");
-  if (numel != h->ps.lay.total)
-    return fail(KDLAE_EPARAM, "flat parameter vector has " + std::to_string(numel) + " floats, expected " +
-                                  std::to_string(h->ps.lay.total));
-  int rc = build_program_a(h);
-  if (rc) return rc;
-  DeviceGuard g(h->device);
-  if ((rc = h->dw.run(params, reinterpret_cast<hipStream_t>(stream)))) return rc;
-  h->committed = true;
-  return KDLAE_OK;
+  return handle_pack_device(h, record_program_a, params, numel, stream);
 }
 
 int64_t asdqe_workspace_bytes(const asdqe_handle* h, int B, int H, int W) {
@@ -311,58 +273,14 @@ int asdqe_forward(asdqe_handle* h, const float* lq, const float* gt, int B, int 
   const int Hp = pl.Hp, Wp = pl.Wp;
   int rc;
   auto conv = [&](const Gemm& g, View in, View o, int Hh, int Ww, int relu) {
-    if (g.kt == 1 && g.ksize == 3 && g.ntiles == 1 && g.cg_per_tap == 1 && g.kgroups == 9 &&
-        g.out_mode == 0) {
-      // 16 -> 16 channels: LDS-tiled kernel with VGPR-resident weights (conv3d_c16.hip)
-      Conv3dC16Params q{};
-      q.in = in.p;
-      q.ldi = in.ld;
-      q.wp = D.P(g.w);
-      q.bias = D.P(g.bias);
-      q.out = o.p;
-      q.ldo = o.ld;
-      q.Bn = B;
-      q.F = 1;
-      q.H = Hh;
-      q.W = Ww;
-      q.relu = relu;
-      q.kt = 1;
-      HIPCHK(launch_conv3d_c16(q, s));
-      return (int)KDLAE_OK;
-    }
-    if (g.ksize == 3 && g.out_mode == 0 && g.kt == 1 && conv_lds_supported(g.kt, g.ntiles, g.cg_per_tap * 16)) {
-      // LDS-tiled implicit GEMM (conv_lds.hip): halo staged once, no per-tap L1 re-reads
-      ConvLdsParams q{};
-      q.in = in.p;
-      q.ldi = in.ld;
-      q.cin_pad = g.cg_per_tap * 16;
-      q.wp = D.P(g.w);
-      q.wp3 = D.P3(g.w3);
-      q.ntiles = g.ntiles;
-      q.kgroups = g.kgroups;
-      q.bias = D.P(g.bias);
-      q.out = o.p;
-      q.ldo = o.ld;
-      q.Bn = B;
-      q.F = 1;
-      q.H = Hh;
-      q.W = Ww;
-      q.kt = g.kt;
-      q.relu = relu;
-      HIPCHK(launch_conv_lds(q, s));
-      return (int)KDLAE_OK;
-    }
     GemmCall c;
-    c.g = &g;
-    c.W = D.P3(g.w3);
-    c.bias = D.P(g.bias);
     c.in = in;
     c.out = o;
     c.B = B;
     c.H = Hh;
     c.Wd = Ww;
     c.relu = relu;
-    return run_gemm(c, s);
+    return run_conv(D, g, c, s);
   };
   // extractors: conv1 (+BN+ReLU) reads the NCHW input with zero padding beyond H x W, conv2 writes merged
   float* e1 = buf(pl.e1);

@@ -16,19 +16,14 @@
 #include <string>
 #include <vector>
 
-#include "param_layout.h"
 #include "runtime.h"
 
 using namespace kdlae;
 
-struct kdlae_s_handle {
+struct kdlae_s_handle : HandleBase {
   kdlae_s_config cfg{};
-  int device = 0;
   int L = 0;               // levels = len(hidden_channels) - 1
   std::vector<int> hc, cs;  // hidden channels, padded to 16
-  ParamStore ps;
-  bool built = false, committed = false;
-  DeviceWeights dw;        // packed arena + the pack program that fills it from the parameters
   struct Block { Gemm a, b; };
   SmallW first;             // encoders.0.0 (Cin = 1), stored padded [cs0][27]
   std::vector<Block> enc, dec;
@@ -93,10 +88,7 @@ int kdlae_s_create(const kdlae_s_config* cfg, int device, kdlae_s_handle** out) 
 
 int kdlae_s_destroy(kdlae_s_handle* h) {
   if (!h) return KDLAE_OK;
-  {
-    DeviceGuard g(h->device);
-    h->dw.release();
-  }
+  handle_release(h);
   delete h;
   return KDLAE_OK;
 }
@@ -104,24 +96,20 @@ int kdlae_s_destroy(kdlae_s_handle* h) {
 int kdlae_s_num_params(const kdlae_s_handle* h) { return h ? (int)h->ps.lay.size() : 0; }
 
 int kdlae_s_param_info(const kdlae_s_handle* h, int index, const char** name, int64_t* numel) {
-  if (!h) return fail(KDLAE_ESTATE, "null handle");
-  return h->ps.lay.info(index, name, numel, nullptr);
+  return handle_param_info(h, index, name, numel);
 }
 
 int64_t kdlae_s_params_numel(const kdlae_s_handle* h) { return h ? h->ps.lay.total : -1; }
 
 int kdlae_s_set_param(kdlae_s_handle* h, const char* name, const float* host_data, int64_t numel) {
-  if (!h || !name || !host_data) return fail(KDLAE_ESTATE, "null argument");
-  return h->ps.set(name, host_data, numel);
+  return handle_set_param(h, name, host_data, numel);
 }
 
 }  // extern "C"
 
-// Records the packed layout (pack program, runtime.h) of this configuration once per handle.
-static int build_program_s(kdlae_s_handle* h) {
-  if (h->built) return KDLAE_OK;
-  PackProgram ar;
-  ar.nsrc = h->ps.lay.total;
+// Records the packed layout (pack program, runtime.h) of this configuration.
+static int record_program_s(HandleBase* base, PackProgram& ar) {
+  auto* h = static_cast<kdlae_s_handle*>(base);
   int err = KDLAE_OK;
   auto conv3d = [&](const std::string& name, int cin, int cout) {
     const int32_t W = h->ps.base(name + ".weight", &err);
@@ -235,43 +223,17 @@ static int build_program_s(kdlae_s_handle* h) {
     h->outc.Cin = h->cs[0];
     h->outc.Cout = 1;
   }
-  if (err) return err;
-  DeviceGuard g(h->device);
-  int rc = h->dw.upload_program(ar);
-  if (rc) return rc;
-  h->built = true;
-  return KDLAE_OK;
+  return err;
 }
 
 extern "C" {
 
-int kdlae_s_commit_params(kdlae_s_handle* h, void* stream) {
-  if (!h) return fail(KDLAE_ESTATE, "null handle");
-  int rc = h->ps.check_complete();
-  if (rc) return rc;
-  if ((rc = build_program_s(h))) return rc;
-  DeviceGuard g(h->device);
-  if ((rc = h->dw.run_host(h->ps.flat(), reinterpret_cast<hipStream_t>(stream)))) return rc;
-  h->committed = true;
-  return KDLAE_OK;
-}
+int kdlae_s_commit_params(kdlae_s_handle* h, void* stream) { return handle_commit(h, record_program_s, stream); }
 
-int kdlae_s_prepare(kdlae_s_handle* h) {
-  if (!h) return fail(KDLAE_ESTATE, "null handle");
-  return build_program_s(h);
-}
+int kdlae_s_prepare(kdlae_s_handle* h) { return handle_prepare(h, record_program_s); }
 
 int kdlae_s_pack_device(kdlae_s_handle* h, const float* params, int64_t numel, void* stream) {
-  if (!h) return fail(KDLAE_ESTATE, "null handle");
-  if (numel != h->ps.lay.total)
-    return fail(KDLAE_EPARAM, "flat parameter vector has " + std::to_string(numel) + " floats, expected " +
-                                  std::to_string(h->ps.lay.total));
-  int rc = build_program_s(h);  // no-op after kdlae_s_prepare
-  if (rc) return rc;
-  DeviceGuard g(h->device);
-  if ((rc = h->dw.run(params, reinterpret_cast<hipStream_t>(stream)))) return rc;
-  h->committed = true;
-  return KDLAE_OK;
+  return handle_pack_device(h, record_program_s, params, numel, stream);
 }
 
 int64_t kdlae_s_workspace_bytes(const kdlae_s_handle* h, int B, int F, int H, int W) {
@@ -304,50 +266,7 @@ int kdlae_s_forward(kdlae_s_handle* h, const float* x, int B, int F, int H, int 
   const DeviceWeights& D = h->dw;
   int rc;
   auto conv = [&](const Gemm& g, View in, View o, int Hh, int Ww, int relu) {
-    if (g.kt == 3 && g.ntiles == 1 && g.cg_per_tap == 1 && g.kgroups == 27) {
-      // 16 -> 16 channels: LDS-tiled kernel with the weights held in VGPRs (conv3d_c16.hip)
-      Conv3dC16Params q{};
-      q.in = in.p;
-      q.ldi = in.ld;
-      q.wp = D.P(g.w);
-      q.bias = D.P(g.bias);
-      q.out = o.p;
-      q.ldo = o.ld;
-      q.Bn = B;
-      q.F = F;
-      q.H = Hh;
-      q.W = Ww;
-      q.relu = relu;
-      q.kt = 3;
-      HIPCHK(launch_conv3d_c16(q, s));
-      return (int)KDLAE_OK;
-    }
-    if (g.ksize == 3 && g.out_mode == 0 && g.kt == 3 && conv_lds_supported(g.kt, g.ntiles, g.cg_per_tap * 16)) {
-      // LDS-tiled implicit GEMM (conv_lds.hip): halo staged once, no per-tap L1 re-reads
-      ConvLdsParams q{};
-      q.in = in.p;
-      q.ldi = in.ld;
-      q.cin_pad = g.cg_per_tap * 16;
-      q.wp = D.P(g.w);
-      q.ntiles = g.ntiles;
-      q.kgroups = g.kgroups;
-      q.bias = D.P(g.bias);
-      q.out = o.p;
-      q.ldo = o.ld;
-      q.Bn = B;
-      q.F = F;
-      q.H = Hh;
-      q.W = Ww;
-      q.kt = g.kt;
-      q.relu = relu;
-      q.wp3 = D.P3(g.w3t);
-      HIPCHK(launch_conv_lds(q, s));
-      return (int)KDLAE_OK;
-    }
     GemmCall c;
-    c.g = &g;
-    c.W = D.P3(g.w3);
-    c.bias = D.P(g.bias);
     c.in = in;
     c.out = o;
     c.B = B;
@@ -355,7 +274,7 @@ int kdlae_s_forward(kdlae_s_handle* h, const float* x, int B, int F, int H, int 
     c.H = Hh;
     c.Wd = Ww;
     c.relu = relu;
-    return run_gemm(c, s);
+    return run_conv(D, g, c, s);
   };
   for (int i = 0; i < h->L; ++i) {
     const int Hi = H >> i, Wi = W >> i, ci = h->cs[i];

@@ -21,7 +21,6 @@
 #include <unordered_map>
 #include <vector>
 
-#include "param_layout.h"
 #include "runtime.h"
 
 namespace kdlae {
@@ -54,14 +53,9 @@ struct BlockW {
 
 using namespace kdlae;
 
-struct kdlae_t_handle {
+struct kdlae_t_handle : HandleBase {
   kdlae_t_config cfg{};
-  int device = 0;
-  ParamStore ps;           // expected state_dict keys (ordered, flat offsets) + host-staged values
-  bool built = false;      // pack program uploaded (depends on the config only)
-  bool committed = false;  // arena filled from parameters at least once
-  DeviceWeights dw;        // packed arena + pack program
-  // model
+  // model (the TransformerBlock stages are listed by stages() below)
   std::vector<BlockW> enc1, enc2, enc3, latent, dec3, dec2, dec1, refinement, refinement_out, enhance;
   SmallW patch_embed, output, output_param, output2, cen, outputen;
   Gemm down1_2, down2_3, down3_4, up4_3, up3_2, up2_1, upen, reduce3, reduce2;
@@ -113,12 +107,42 @@ static int validate(const kdlae_t_config& c) {
   return KDLAE_OK;
 }
 
+// The TransformerBlock stages in the order kdlae_t_forward runs them: state_dict prefix, block count,
+// channels, heads, resolution relative to the input as num / den, and the handle's vector of packed
+// blocks.  The one statement of the topology: record_program packs from it, make_plan sizes the
+// per-block scratch from it and the debug taps are named from it (Fwd::run spells out the glue).
+struct Stage {
+  const char* name;
+  int count, C, heads, num, den;
+  std::vector<BlockW> kdlae_t_handle::*blocks;
+  bool packed;  // the module has it (its keys are in the state_dict): packed, and counted by make_plan
+  bool runs;    // the forward runs it: refinement_out only for params == "cat", enhance only for static == "train"
+};
+static std::vector<Stage> stages(const kdlae_t_config& c) {
+  using H = kdlae_t_handle;
+  const int d = c.dim, nr = c.num_refinement_blocks;
+  const int *nb = c.num_blocks, *hd = c.heads;
+  const bool cat = c.params_cat != 0, sr = c.static_train != 0;
+  return {
+      {"encoder_level1", nb[0], d, hd[0], 1, 1, &H::enc1, true, true},
+      {"encoder_level2", nb[1], 2 * d, hd[1], 1, 2, &H::enc2, true, true},
+      {"encoder_level3", nb[2], 4 * d, hd[2], 1, 4, &H::enc3, true, true},
+      {"latent", nb[3], 8 * d, hd[3], 1, 8, &H::latent, true, true},
+      {"decoder_level3", nb[2], 4 * d, hd[2], 1, 4, &H::dec3, true, true},
+      {"decoder_level2", nb[1], 2 * d, hd[1], 1, 2, &H::dec2, true, true},
+      {"decoder_level1", nb[0], 2 * d, hd[0], 1, 1, &H::dec1, true, true},
+      {"refinement", nr, 2 * d, hd[0], 1, 1, &H::refinement, true, true},
+      {"refinement_out", nr, 2 * d, hd[0], 1, 1, &H::refinement_out, true, cat},
+      {"enhance", nr, d, hd[0], 2, 1, &H::enhance, sr, sr},
+  };
+}
+
 // ----------------------------------------------------------------------------- packing helpers
 // The packer records the device layout as a pack program (runtime.h): every packed float names the
 // flat-parameter entries it is gathered from.  Values are produced on the device (pack.hip).
 struct Packer {
   kdlae_t_handle* h;
-  PackProgram prog;
+  PackProgram& prog;
   int err = KDLAE_OK;
 
   int32_t get(const std::string& k) { return h->ps.base(k, &err); }
@@ -335,9 +359,9 @@ struct Packer {
     return b;
   }
 
-  std::vector<BlockW> stage(const std::string& n, int cnt, int C, int heads) {
+  std::vector<BlockW> stage(const Stage& st) {
     std::vector<BlockW> v;
-    for (int i = 0; i < cnt; ++i) v.push_back(block(n + "." + std::to_string(i), C, heads));
+    for (int i = 0; i < st.count; ++i) v.push_back(block(st.name + ("." + std::to_string(i)), st.C, st.heads));
     return v;
   }
 };
@@ -354,8 +378,6 @@ struct Plan : WsPlan {
 // at least 32 rows (512^2: 64 rows, the 2-row halo costs 3%; 1024^2: 128 rows; 4 and 16 segments
 // measured no better, profiles/r02_gram_nseg_probe.txt); generic kernel: 64-pixel steps grouped 16
 // per slot.
-constexpr auto KDLAE_T_DOWN_LDS = 1;  // Downsample convs on conv_lds (0: the implicit GEMM)
-constexpr auto KDLAE_T_UP_LDS = 1;  // Upsample convs on conv_lds (0: the implicit GEMM)
 constexpr int kGramMaxSeg = 8, kGramMinRows = 32;  // Gram slots: row segments per strip, rows per segment
 int nslots_for(int H, int W) {
   if (W % 16 == 0) {
@@ -383,12 +405,13 @@ static Plan make_plan(const kdlae_t_handle* h, int B, int H, int W) {
   pl.refo = pl.take(P1 * 2 * d);
   pl.cenb = c.static_train ? pl.take(P1 * 2 * d) : 0;
   pl.srs = c.static_train ? pl.take(Psr * d) : 0;
-  // per-block scratch: max over every stage that runs
+  // per-block scratch: max over every packed stage (refinement_out too when the forward skips it)
   long long mq = 0, mv = 0, mfp = 0, mfg = 0, mst = 0, mpart = 0, mred = 0, mM = 0;
-  auto acc = [&](const std::vector<BlockW>& st, long long P, int Hh, int Ww) {
-    for (const BlockW& b : st) {
-      const int CT = b.Ch / 16;
-      const long long slot = (long long)CT * CT * 256 + 2 * b.Ch;
+  for (const Stage& st : stages(c)) {
+    const int Hh = H * st.num / st.den, Ww = W * st.num / st.den;
+    const long long P = (long long)B * Hh * Ww;
+    for (const BlockW& b : h->*st.blocks) {
+      const long long slot = gram_slot_floats(b.Ch);
       mq = std::max(mq, P * 3 * b.C);
       mv = std::max(mv, P * b.C);
       mfp = std::max(mfp, P * 2 * b.hidS);
@@ -396,19 +419,9 @@ static Plan make_plan(const kdlae_t_handle* h, int B, int H, int W) {
       mst = std::max(mst, P * 2);
       mpart = std::max(mpart, (long long)B * b.heads * nslots_for(Hh, Ww) * slot);
       mred = std::max(mred, (long long)B * b.heads * slot);
-      mM = std::max(mM, (long long)B * split3_floats(b.C / 16, b.C / 16));
+      mM = std::max(mM, (long long)B * folded_proj_floats(b.C));
     }
-  };
-  acc(h->enc1, P1, H, W);
-  acc(h->enc2, P2, H / 2, W / 2);
-  acc(h->enc3, P3, H / 4, W / 4);
-  acc(h->latent, P4, H / 8, W / 8);
-  acc(h->dec3, P3, H / 4, W / 4);
-  acc(h->dec2, P2, H / 2, W / 2);
-  acc(h->dec1, P1, H, W);
-  acc(h->refinement, P1, H, W);
-  acc(h->refinement_out, P1, H, W);
-  acc(h->enhance, Psr, 2 * H, 2 * W);
+  }
   pl.qkv = pl.take(mq);
   pl.vbuf = pl.take(mv);
   pl.fpre = pl.take(mfp);
@@ -457,19 +470,19 @@ struct Fwd {
     return KDLAE_OK;
   }
 
-  // GEMM launch on views (probe-wrapped)
+  // GEMM / conv launch on views (probe-wrapped); run_conv picks the kernel.  The Downsample and
+  // Upsample convs (3x3, PixelUnshuffle / PixelShuffle store) take the LDS-tiled conv (conv_lds.hip):
+  // the implicit GEMM gathers every input pixel through L1 for each of the 9 taps and, with 24..96
+  // outputs, feeds each gathered fragment to only 2..6 MFMAs
   int gemm(const Gemm& g, const float* W, long long w_img_stride, View in, int Hh, int Ww, View out,
            int out_mode, const float* R, int ldr, int ln, int ln_C, int probeC) {
     const int HW = Hh * Ww;
     GemmCall c;
-    c.g = &g;
     c.W = W;
     c.w_img_stride = w_img_stride;
-    c.bias = h->P(g.bias);
     c.in = in;
     c.out = out;
     c.B = B;
-    c.F = 1;
     c.H = Hh;
     c.Wd = Ww;
     c.out_mode = out_mode;
@@ -480,66 +493,39 @@ struct Fwd {
     c.stats_buf = buf(pl.stats);
     int rc = probe_begin(1, probeC);
     if (rc) return rc;
-    // the Downsample convs (3x3, PixelUnshuffle store) on the LDS-tiled conv (conv_lds.hip): the
-    // implicit GEMM gathers every input pixel through L1 for each of the 9 taps and, with 24..96
-    // outputs, feeds each gathered fragment to only 2..6 MFMAs
-    const bool lds_conv = g.ksize == 3 && ((KDLAE_T_DOWN_LDS && out_mode == 1) || (KDLAE_T_UP_LDS && out_mode == 2)) &&
-                          !R && !ln && conv_lds_supported(1, g.ntiles, g.cg_per_tap * 16);
     if (h->probe_class == 1)
       tag = "gemm C" + std::to_string(probeC) + " HW" + std::to_string(HW) + " N" + std::to_string(g.n_true) + " K" +
             std::to_string(g.k_true) + " k" + std::to_string(g.ksize) +
-            (lds_conv ? std::string(" conv_lds") : " v" + std::to_string(g.NT) + "x" + std::to_string(g.KG) +
-                                                       (g.group_tiles ? "r" : "c") + "w" + std::to_string(g.WPE)) +
+            (conv_kernel(g, c) == ConvKernel::lds
+                 ? std::string(" conv_lds")
+                 : " v" + std::to_string(g.NT) + "x" + std::to_string(g.KG) + (g.group_tiles ? "r" : "c") + "w" +
+                       std::to_string(g.WPE)) +
             (ln ? " ln" : "") + (R ? " res" : "");
-    if (lds_conv) {
-      ConvLdsParams q{};
-      q.in = in.p;
-      q.ldi = in.ld;
-      q.cin_pad = g.cg_per_tap * 16;
-      q.wp = h->P(g.w);
-      q.wp3 = W;
-      q.ntiles = g.ntiles;
-      q.kgroups = g.kgroups;
-      q.bias = h->P(g.bias);
-      q.out = out.p;
-      q.ldo = out.ld;
-      q.Bn = B;
-      q.F = 1;
-      q.H = Hh;
-      q.W = Ww;
-      q.kt = 1;
-      q.relu = 0;
-      q.out_mode = out_mode;
-      q.nout = g.n_true;
-      HIPCHK(launch_conv_lds(q, s));
-    } else if ((rc = run_gemm(c, s))) {
-      return rc;
-    }
+    if ((rc = run_conv(h->dw, g, c, s))) return rc;
     const double P = (double)B * HW;
     const double kin = g.ksize == 3 ? g.k_true / 9.0 : g.k_true;
     const double bytes = 4.0 * (P * kin + P * g.n_true * (R ? 2.0 : 1.0) + (double)g.n_true * g.k_true);
     return probe_end(1, probeC, bytes, 2.0 * P * g.n_true * g.k_true);
   }
 
-  // One TransformerBlock (:159-163) in place on x, or — with ffn (b.ffn_fused) — its attention half in
-  // place and its feed-forward half from x into *ffn (which must not overlap x).
-  int block(const BlockW& b, View x, int Hh, int Ww, const View* ffn = nullptr) {
+  int ln() const { return h->cfg.layernorm_biasfree ? 1 : 2; }
+
+  // The Gram pass of a block's attention: the per-image folded projection M lands in pl.Mp.  Either
+  // the fused MDTA pass 1, or the qkv GEMM + the Gram ring.  The ring leaves v' = dw3x3(v) in pl.vbuf,
+  // except with *dw_out (asked for with want_dw_out): then v stays in the qkv buffer for attn_out_dw.
+  int gram_pass(const BlockW& b, View x, int Hh, int Ww, bool want_dw_out, bool* dw_out) {
     const int HW = Hh * Ww;
-    const int ln = h->cfg.layernorm_biasfree ? 1 : 2;
     const long long P = (long long)B * HW;
+    const int nslots = nslots_for(Hh, Ww), slot_floats = gram_slot_floats(b.Ch);
+    const GramSegs sg = gram_segments(nslots, Hh, Ww);
     int rc;
-    // --- attention
-    const int nslots = nslots_for(Hh, Ww);
-    const int nseg = Ww % 16 == 0 ? nslots / (Ww / 16) : 0;
-    const int seg_rows = nseg ? (Hh + nseg - 1) / nseg : 0;
-    bool dw_out = false;  // no-v ring + attn_out_dw in place of the v-writing ring + the M GEMM
-    if (b.mdta_fused && mdta_fused_supported(b.C, b.heads, Hh, Ww, nseg, seg_rows)) {
+    *dw_out = false;
+    if (b.mdta_fused && mdta_fused_supported(b.C, b.heads, Hh, Ww, sg.nseg, sg.seg_rows)) {
       // LN + qkv + dwconv + Gram in one pass (mdta_fused.hip): qkv never reaches HBM
-      const int CT = b.Ch / 16;
       MdtaFusedParams q{};
       q.x = x.p;
       q.ldx = x.ld;
-      q.ln = ln;
+      q.ln = ln();
       q.Wqkv = h->P3(b.qkv.w3);
       q.bias = h->P(b.qkv.bias);
       q.wdw = h->P(b.dwqkv);
@@ -548,9 +534,9 @@ struct Fwd {
       q.ldv = b.C;
       q.partial = buf(pl.part);
       q.nslots = nslots;
-      q.slot_floats = CT * CT * 256 + 2 * b.Ch;
-      q.nseg = nseg;
-      q.seg_rows = seg_rows;
+      q.slot_floats = slot_floats;
+      q.nseg = sg.nseg;
+      q.seg_rows = sg.seg_rows;
       q.Bn = B;
       q.H = Hh;
       q.W = Ww;
@@ -561,45 +547,51 @@ struct Fwd {
       if ((rc = probe_end(2, b.C, 4.0 * P * 2 * b.C,
                           2.0 * P * (3.0 * b.C * b.C + 27.0 * b.C + (double)b.C * b.Ch))))
         return rc;
-      HIPCHK(launch_gram_reduce(q.partial, buf(pl.red), B, b.heads, nslots, q.slot_floats, s));
-      HIPCHK(launch_attn_fold(buf(pl.red), q.slot_floats, h->P(b.proj), h->P(b.temp), buf(pl.Mp), B, b.C, b.heads, s));
     } else {
-    View qkv{buf(pl.qkv), 3 * b.C};
-    dw_out = ffn && b.attn_out_dw && attn_out_dw_supported(b.C, Hh, Ww, qkv.ld);
-    rc = gemm(b.qkv, h->P3(b.qkv.w3), 0, x, Hh, Ww, qkv, 0, nullptr, 0, ln, b.C, b.C);
-    if (rc) return rc;
-    GramParams gp{};
-    gp.qkv = qkv.p;
-    gp.ld = qkv.ld;
-    gp.wdw = h->P(b.dwqkv);
-    gp.bdw = h->P(b.dwqkv_b);
-    gp.v_out = buf(pl.vbuf);
-    gp.ldv = b.C;
-    gp.partial = buf(pl.part);
-    gp.C = b.C;
-    gp.heads = b.heads;
-    gp.Ch = b.Ch;
-    gp.Bn = B;
-    gp.H = Hh;
-    gp.W = Ww;
-    gp.nslots = nslots;
-    gp.zeros = h->P(h->zeros);
-    const int CT = b.Ch / 16;
-    gp.slot_floats = CT * CT * 256 + 2 * b.Ch;
-    dw_out = dw_out && gram_ring_applies(gp);
-    gp.no_v = dw_out ? 1 : 0;
-    if ((rc = probe_begin(2, b.C))) return rc;
-    tag = "gram C" + std::to_string(b.C) + " Ch" + std::to_string(b.Ch) + " HW" + std::to_string(HW) + (dw_out ? " qk" : "");
-    HIPCHK(launch_dwconv_gram(gp, s));
-    // algorithmic: read q | k | v, write v; without v read q | k only
-    rc = dw_out ? probe_end(2, b.C, 4.0 * P * 2 * b.C, 2.0 * P * (18.0 * b.C + (double)b.C * b.Ch))
-                : probe_end(2, b.C, 4.0 * P * 4 * b.C, 2.0 * P * (27.0 * b.C + (double)b.C * b.Ch));
-    if (rc) return rc;
-    HIPCHK(launch_gram_reduce(gp.partial, buf(pl.red), B, b.heads, gp.nslots, gp.slot_floats, s));
-    HIPCHK(launch_attn_fold(buf(pl.red), gp.slot_floats, h->P(b.proj), h->P(b.temp), buf(pl.Mp), B, b.C, b.heads, s));
+      View qkv{buf(pl.qkv), 3 * b.C};
+      rc = gemm(b.qkv, h->P3(b.qkv.w3), 0, x, Hh, Ww, qkv, 0, nullptr, 0, ln(), b.C, b.C);
+      if (rc) return rc;
+      GramParams gp{};
+      gp.qkv = qkv.p;
+      gp.ld = qkv.ld;
+      gp.wdw = h->P(b.dwqkv);
+      gp.bdw = h->P(b.dwqkv_b);
+      gp.v_out = buf(pl.vbuf);
+      gp.ldv = b.C;
+      gp.partial = buf(pl.part);
+      gp.C = b.C;
+      gp.heads = b.heads;
+      gp.Ch = b.Ch;
+      gp.Bn = B;
+      gp.H = Hh;
+      gp.W = Ww;
+      gp.nslots = nslots;
+      gp.zeros = h->P(h->zeros);
+      gp.slot_floats = slot_floats;
+      *dw_out = want_dw_out && b.attn_out_dw && attn_out_dw_supported(b.C, Hh, Ww, qkv.ld) && gram_ring_applies(gp);
+      gp.no_v = *dw_out ? 1 : 0;
+      if ((rc = probe_begin(2, b.C))) return rc;
+      tag = "gram C" + std::to_string(b.C) + " Ch" + std::to_string(b.Ch) + " HW" + std::to_string(HW) +
+            (*dw_out ? " qk" : "");
+      HIPCHK(launch_dwconv_gram(gp, s));
+      // algorithmic: read q | k | v, write v; without v read q | k only
+      rc = *dw_out ? probe_end(2, b.C, 4.0 * P * 2 * b.C, 2.0 * P * (18.0 * b.C + (double)b.C * b.Ch))
+                   : probe_end(2, b.C, 4.0 * P * 4 * b.C, 2.0 * P * (27.0 * b.C + (double)b.C * b.Ch));
+      if (rc) return rc;
     }
-    View fpre{buf(pl.fpre), 2 * b.hidS};
-    const bool fuse_in = b.fused_attn_in && !ffn;
+    HIPCHK(launch_gram_reduce(buf(pl.part), buf(pl.red), B, b.heads, nslots, slot_floats, s));
+    HIPCHK(launch_attn_fold(buf(pl.red), slot_floats, h->P(b.proj), h->P(b.temp), buf(pl.Mp), B, b.C, b.heads, s));
+    return KDLAE_OK;
+  }
+
+  View fpre(const BlockW& b) { return View{buf(pl.fpre), 2 * b.hidS}; }  // project_in's output
+
+  // The attention output x1 = x + M v' (+ bias) in place on x: fused with LN + project_in into fpre
+  // (fuse_in), with v's depthwise 3x3 as its prologue (dw_out), or the per-image-weight GEMM.
+  int attn_out(const BlockW& b, View x, int Hh, int Ww, bool fuse_in, bool dw_out) {
+    const int HW = Hh * Ww;
+    const double Pd = (double)B * HW;
+    int rc;
     if (fuse_in) {
       // x1 = x + M v written back into x, LN(x1) -> project_in into fpre, one kernel
       const Gemm& g0 = b.attn_in_split ? b.pin_g0 : b.pin;
@@ -608,18 +600,18 @@ struct Fwd {
       c.W = h->P3(g0.w3);
       c.bias = h->P(g0.bias);
       c.in = View{buf(pl.vbuf), b.C};
-      c.out = fpre;
+      c.out = fpre(b);
       c.B = B;
       c.F = 1;
       c.H = Hh;
       c.Wd = Ww;
       c.R = x.p;
       c.ldr = x.ld;
-      c.ln = ln;
+      c.ln = ln();
       c.ln_C = b.C;
       c.stats_buf = buf(pl.stats);
       c.Wm = buf(pl.Mp);
-      c.wm_img_stride = split3_floats(b.C / 16, b.C / 16);
+      c.wm_img_stride = folded_proj_floats(b.C);
       c.bias_m = h->P(b.proj_b);
       c.out1 = x;
       if ((rc = probe_begin(1, b.C))) return rc;
@@ -628,17 +620,16 @@ struct Fwd {
               " K" + std::to_string(b.C) + " attn_out+ln+project_in v" + std::to_string(g0.NT) + "x" +
               std::to_string(g0.KG);
       if ((rc = run_gemm(c, s))) return rc;
-      const double Pd = (double)P;
       // read v and x, write x1 and the project_in rows; M per image + W_in; both GEMMs' FLOPs
       const double bytes = 4.0 * (Pd * 3.0 * b.C + Pd * g0.n_true + (double)B * b.C * b.C +
                                   (double)g0.n_true * b.C);
       if ((rc = probe_end(1, b.C, bytes, 2.0 * Pd * ((double)b.C * b.C + (double)b.C * g0.n_true)))) return rc;
-      if (b.attn_in_split) {  // project_in's second weight group on x1 (now in x)
-        rc = gemm(b.pin_g1, h->P3(b.pin_g1.w3), 0, x, Hh, Ww, View{fpre.p + 16 * b.pin_g0.ntiles, fpre.ld}, 0, nullptr,
-                  0, ln, b.C, b.C);
-        if (rc) return rc;
-      }
-    } else if (dw_out) {
+      if (!b.attn_in_split) return KDLAE_OK;
+      // project_in's second weight group on x1 (now in x)
+      return gemm(b.pin_g1, h->P3(b.pin_g1.w3), 0, x, Hh, Ww, View{fpre(b).p + 16 * b.pin_g0.ntiles, fpre(b).ld}, 0,
+                  nullptr, 0, ln(), b.C, b.C);
+    }
+    if (dw_out) {
       // x1 = x + M dw3x3(v) in place, v read where the qkv GEMM left it: vbuf is not touched
       AttnOutDwParams q{};
       q.v = buf(pl.qkv) + 2 * b.C;
@@ -647,7 +638,7 @@ struct Fwd {
       q.ldw = 3 * b.C;
       q.bdw = b.dwqkv_b != kNone ? h->P(b.dwqkv_b) + 2 * b.C : nullptr;
       q.M = buf(pl.Mp);
-      q.m_img_stride = split3_floats(b.C / 16, b.C / 16);
+      q.m_img_stride = folded_proj_floats(b.C);
       q.bias = h->P(b.proj_gemm.bias);
       q.R = x.p;
       q.ldr = x.ld;
@@ -662,25 +653,26 @@ struct Fwd {
         tag = "attn_out_dw C" + std::to_string(b.C) + " HW" + std::to_string(HW) + " N" + std::to_string(b.C) + " K" +
               std::to_string(b.C) + " res";
       HIPCHK(launch_attn_out_dw(q, b.C, s));
-      const double Pd = (double)P;
       // algorithmic: read v and x, write x1; M per image; the stencil's and the product's FLOPs
-      if ((rc = probe_end(1, b.C, 4.0 * (Pd * 3.0 * b.C + (double)B * b.C * b.C), 2.0 * Pd * (9.0 * b.C + (double)b.C * b.C))))
-        return rc;
-    } else {
-      rc = gemm(b.proj_gemm, buf(pl.Mp), split3_floats(b.C / 16, b.C / 16), View{buf(pl.vbuf), b.C}, Hh, Ww, x, 0,
-                x.p, x.ld, 0,
-                0, b.C);
-      if (rc) return rc;
+      return probe_end(1, b.C, 4.0 * (Pd * 3.0 * b.C + (double)B * b.C * b.C), 2.0 * Pd * (9.0 * b.C + (double)b.C * b.C));
     }
-    // --- feed-forward
-    if ((rc = tap(x, b.C, Hh, Ww))) return rc;  // x1 (diagnostics only)
+    return gemm(b.proj_gemm, buf(pl.Mp), folded_proj_floats(b.C), View{buf(pl.vbuf), b.C}, Hh, Ww, x, 0, x.p, x.ld, 0,
+                0, b.C);
+  }
+
+  // The feed-forward half on x1 (in x): the fused kernel from x into *ffn, or in place on x project_in
+  // (unless attn_out already ran it: fuse_in) + the fused GDFN tail or gate + project_out.
+  int feed_forward(const BlockW& b, View x, int Hh, int Ww, bool fuse_in, const View* ffn) {
+    const int HW = Hh * Ww;
+    const long long P = (long long)B * HW;
+    int rc;
     if (ffn) {
       FfnParams q{};
       q.x = x.p;
       q.ldx = x.ld;
       q.out = ffn->p;
       q.ldo = ffn->ld;
-      q.ln = ln;
+      q.ln = ln();
       q.hidS = b.hidS;
       q.Win = h->P3(b.pin.w3);
       q.bias_in = h->P(b.pin.bias);
@@ -698,13 +690,13 @@ struct Fwd {
                        2.0 * P * ((double)b.C * 2.0 * b.hid + 18.0 * b.hid + (double)b.hid * b.C));
     }
     if (!fuse_in) {
-      rc = gemm(b.pin, h->P3(b.pin.w3), 0, x, Hh, Ww, fpre, 0, nullptr, 0, ln, b.C, b.C);
+      rc = gemm(b.pin, h->P3(b.pin.w3), 0, x, Hh, Ww, fpre(b), 0, nullptr, 0, ln(), b.C, b.C);
       if (rc) return rc;
     }
     if (b.fused_gdfn) {
       GdfnParams gd{};
-      gd.x = fpre.p;
-      gd.ld = fpre.ld;
+      gd.x = fpre(b).p;
+      gd.ld = fpre(b).ld;
       gd.hidS = b.hidS;
       gd.dw = h->P(b.dwffn);
       gd.Wp = h->P3(b.pout.w3);
@@ -725,8 +717,8 @@ struct Fwd {
                        2.0 * P * (18.0 * b.hid + (double)b.hid * b.C));
     }
     GateParams ga{};
-    ga.x = fpre.p;
-    ga.ld = fpre.ld;
+    ga.x = fpre(b).p;
+    ga.ld = fpre(b).ld;
     ga.hidS = b.hidS;
     ga.w = h->P(b.dwffn);
     ga.b = h->P(b.dwffn_b);
@@ -740,6 +732,18 @@ struct Fwd {
     HIPCHK(launch_dwconv_gate(ga, s));
     if ((rc = probe_end(3, b.C, 4.0 * P * 3 * b.hid, 2.0 * P * 18.0 * b.hid))) return rc;
     return gemm(b.pout, h->P3(b.pout.w3), 0, View{buf(pl.fg), b.hidS}, Hh, Ww, x, 0, x.p, x.ld, 0, 0, b.C);
+  }
+
+  // One TransformerBlock (:159-163) in place on x, or — with ffn (b.ffn_fused) — its attention half in
+  // place and its feed-forward half from x into *ffn (which must not overlap x).
+  int block(const BlockW& b, View x, int Hh, int Ww, const View* ffn = nullptr) {
+    const bool fuse_in = b.fused_attn_in && !ffn;
+    bool dw_out = false;  // no-v ring + attn_out_dw in place of the v-writing ring + the M GEMM
+    int rc;
+    if ((rc = gram_pass(b, x, Hh, Ww, ffn != nullptr, &dw_out))) return rc;
+    if ((rc = attn_out(b, x, Hh, Ww, fuse_in, dw_out))) return rc;
+    if ((rc = tap(x, b.C, Hh, Ww))) return rc;  // x1 (diagnostics only)
+    return feed_forward(b, x, Hh, Ww, fuse_in, ffn);
   }
 
   // kdlae_t_debug_taps: taps passed so far in this forward; the order is tap_list's (per stage: its
@@ -910,9 +914,9 @@ int kdlae_t_create(const kdlae_t_config* cfg, int device, kdlae_t_handle** out) 
 
 int kdlae_t_destroy(kdlae_t_handle* h) {
   if (!h) return KDLAE_OK;
+  handle_release(h);
   {
     DeviceGuard g(h->device);
-    h->dw.release();
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
   }
   delete h;
@@ -922,95 +926,55 @@ int kdlae_t_destroy(kdlae_t_handle* h) {
 int kdlae_t_num_params(const kdlae_t_handle* h) { return h ? (int)h->ps.lay.size() : 0; }
 
 int kdlae_t_param_info(const kdlae_t_handle* h, int index, const char** name, int64_t* numel) {
-  if (!h) return fail(KDLAE_ESTATE, "null handle");
-  return h->ps.lay.info(index, name, numel, nullptr);
+  return handle_param_info(h, index, name, numel);
 }
 
 int64_t kdlae_t_params_numel(const kdlae_t_handle* h) { return h ? h->ps.lay.total : -1; }
 
 int kdlae_t_set_param(kdlae_t_handle* h, const char* name, const float* host_data, int64_t numel) {
-  if (!h || !name || !host_data) return fail(KDLAE_ESTATE, "null argument");
-  return h->ps.set(name, host_data, numel);
+  return handle_set_param(h, name, host_data, numel);
 }
 
 }  // extern "C"
 
-// Records the packed layout of this configuration (once per handle) and uploads the program.
-static int build_program(kdlae_t_handle* h) {
-  if (h->built) return KDLAE_OK;
+// Records the packed layout of this configuration: the glue layers, then every packed stage.
+static int record_program(HandleBase* base, PackProgram& prog) {
+  auto* h = static_cast<kdlae_t_handle*>(base);
   const kdlae_t_config& c = h->cfg;
-  Packer pk{h};
-  pk.prog.nsrc = h->ps.lay.total;
-  h->zeros = pk.prog.add(std::vector<PEx>(64));
+  Packer pk{h, prog};
+  h->zeros = prog.add(std::vector<PEx>(64));
   const int d = c.dim;
-  const int* nb = c.num_blocks;
-  const int* hd = c.heads;
-  const int nr = c.num_refinement_blocks;
   h->patch_embed = pk.small("patch_embed.proj", d, c.inp_channels, false);
-  h->enc1 = pk.stage("encoder_level1", nb[0], d, hd[0]);
   h->down1_2 = pk.conv3("down1_2.body.0", d / 2, d, 1);
-  h->enc2 = pk.stage("encoder_level2", nb[1], 2 * d, hd[1]);
   h->down2_3 = pk.conv3("down2_3.body.0", d, 2 * d, 1);
-  h->enc3 = pk.stage("encoder_level3", nb[2], 4 * d, hd[2]);
   h->down3_4 = pk.conv3("down3_4.body.0", 2 * d, 4 * d, 1);
-  h->latent = pk.stage("latent", nb[3], 8 * d, hd[3]);
   h->up4_3 = pk.conv3("up4_3.body.0", 16 * d, 8 * d, 2);
   h->reduce3 = pk.pointwise("reduce_chan_level3", 4 * d, 8 * d, 8 * d, 4 * d, [](int n) { return n; }, "", c.bias, false);
-  h->dec3 = pk.stage("decoder_level3", nb[2], 4 * d, hd[2]);
   h->up3_2 = pk.conv3("up3_2.body.0", 8 * d, 4 * d, 2);
   h->reduce2 = pk.pointwise("reduce_chan_level2", 2 * d, 4 * d, 4 * d, 2 * d, [](int n) { return n; }, "", c.bias, false);
-  h->dec2 = pk.stage("decoder_level2", nb[1], 2 * d, hd[1]);
   h->up2_1 = pk.conv3("up2_1.body.0", 4 * d, 2 * d, 2);
-  h->dec1 = pk.stage("decoder_level1", nb[0], 2 * d, hd[0]);
-  h->refinement = pk.stage("refinement", nr, 2 * d, hd[0]);
   h->output = pk.small("output", c.out_channels, 2 * d, c.bias);
   h->output_param = pk.small("output_param", 2 * d, c.out_channels + 1, c.bias);
-  h->refinement_out = pk.stage("refinement_out", nr, 2 * d, hd[0]);
   h->output2 = pk.small("output2", c.out_channels, 2 * d, c.bias);
   if (c.static_train) {
     const int hc = 2 * d;
     h->cen = pk.small("cen", hc, c.out_channels, c.bias);
     h->upen = pk.conv3("upen.body.0", 2 * hc, hc, 2);
-    h->enhance = pk.stage("enhance", nr, hc / 2, hd[0]);
     h->outputen = pk.small("outputen", c.out_channels, hc / 2, c.bias);
   }
-  if (pk.err) return pk.err;
-  DeviceGuard g(h->device);
-  int rc = h->dw.upload_program(pk.prog);
-  if (rc) return rc;
-  h->built = true;
-  return KDLAE_OK;
+  for (const Stage& st : stages(c))
+    if (st.packed) h->*st.blocks = pk.stage(st);
+  return pk.err;
 }
 
 extern "C" {
 
-int kdlae_t_commit_params(kdlae_t_handle* h, void* stream) {
-  if (!h) return fail(KDLAE_ESTATE, "null handle");
-  int rc = h->ps.check_complete();
-  if (rc) return rc;
-  if ((rc = build_program(h))) return rc;
-  DeviceGuard g(h->device);
-  if ((rc = h->dw.run_host(h->ps.flat(), reinterpret_cast<hipStream_t>(stream)))) return rc;
-  h->committed = true;
-  return KDLAE_OK;
-}
+int kdlae_t_commit_params(kdlae_t_handle* h, void* stream) { return handle_commit(h, record_program, stream); }
 
-int kdlae_t_prepare(kdlae_t_handle* h) {
-  if (!h) return fail(KDLAE_ESTATE, "null handle");
-  return build_program(h);
-}
+int kdlae_t_prepare(kdlae_t_handle* h) { return handle_prepare(h, record_program); }
 
 int kdlae_t_pack_device(kdlae_t_handle* h, const float* params, int64_t numel, void* stream) {
-  if (!h) return fail(KDLAE_ESTATE, "null handle");
-  if (numel != h->ps.lay.total)
-    return fail(KDLAE_EPARAM, "flat parameter vector has " + std::to_string(numel) + " floats, expected " +
-                                  std::to_string(h->ps.lay.total));
-  int rc = build_program(h);
-  if (rc) return rc;
-  DeviceGuard g(h->device);
-  if ((rc = h->dw.run(params, reinterpret_cast<hipStream_t>(stream)))) return rc;
-  h->committed = true;
-  return KDLAE_OK;
+  return handle_pack_device(h, record_program, params, numel, stream);
 }
 
 int64_t kdlae_t_workspace_bytes(const kdlae_t_handle* h, int B, int H, int W) {
@@ -1041,31 +1005,20 @@ int kdlae_t_forward(kdlae_t_handle* h, const float* img, const float* rate, int 
   return f.run(img, rate, H, W, hq, sr);
 }
 
-// TransformerBlocks in the order kdlae_t_forward runs them: (state_dict prefix, channels, resolution
-// relative to the input as num / den)
+// The debug taps in the order kdlae_t_forward passes them: per stage that runs, its input, then per
+// block the attention half's output and the block output (name, channels, resolution as num / den)
 struct TapInfo { std::string name; int C, num, den; };
 static std::vector<TapInfo> tap_list(const kdlae_t_handle* h) {
-  const kdlae_t_config& c = h->cfg;
-  const int d = c.dim, nr = c.num_refinement_blocks;
   std::vector<TapInfo> v;
-  auto add = [&](const char* n, int cnt, int C, int num, int den) {
-    if (cnt <= 0) return;
-    v.push_back({std::string(n) + ".in", C, num, den});
-    for (int i = 0; i < cnt; ++i) {
-      v.push_back({std::string(n) + "." + std::to_string(i) + ".attn", C, num, den});
-      v.push_back({std::string(n) + "." + std::to_string(i), C, num, den});
+  for (const Stage& st : stages(h->cfg)) {
+    if (!st.runs || st.count <= 0) continue;
+    const std::string n = st.name;
+    v.push_back({n + ".in", st.C, st.num, st.den});
+    for (int i = 0; i < st.count; ++i) {
+      v.push_back({n + "." + std::to_string(i) + ".attn", st.C, st.num, st.den});
+      v.push_back({n + "." + std::to_string(i), st.C, st.num, st.den});
     }
-  };
-  add("encoder_level1", c.num_blocks[0], d, 1, 1);
-  add("encoder_level2", c.num_blocks[1], 2 * d, 1, 2);
-  add("encoder_level3", c.num_blocks[2], 4 * d, 1, 4);
-  add("latent", c.num_blocks[3], 8 * d, 1, 8);
-  add("decoder_level3", c.num_blocks[2], 4 * d, 1, 4);
-  add("decoder_level2", c.num_blocks[1], 2 * d, 1, 2);
-  add("decoder_level1", c.num_blocks[0], 2 * d, 1, 1);
-  add("refinement", nr, 2 * d, 1, 1);
-  if (c.params_cat) add("refinement_out", nr, 2 * d, 1, 1);
-  if (c.static_train) add("enhance", nr, d, 2, 1);
+  }
   return v;
 }
 

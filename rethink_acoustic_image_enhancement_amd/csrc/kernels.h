@@ -99,6 +99,17 @@ struct SmallOutParams {            // 3x3 (ks=3) or pointwise (ks=1) conv with C
   const float* res_nhwc; int ldr;      // NHWC residual added before the store (NHWC mode; may alias out)
 };
 
+// Floats of one partial Gram slot of a head with Ch channels: the Ch x Ch product as 16 x 16 tiles of 256,
+// then |q|^2 and |k|^2 per channel.
+inline int gram_slot_floats(int Ch) { return (Ch / 16) * (Ch / 16) * 256 + 2 * Ch; }
+// Row segments per 16-column strip, and rows per segment, of the strip kernels' slot partition at
+// nslots slots per (image, head); nseg = 0 when W is no multiple of 16 (the generic kernel's partition).
+struct GramSegs { int nseg, seg_rows; };
+inline GramSegs gram_segments(int nslots, int H, int W) {
+  const int nseg = W % 16 == 0 ? nslots / (W / 16) : 0;
+  return {nseg, nseg ? (H + nseg - 1) / nseg : 0};
+}
+
 bool gemm_attn_in_variant(int NT, int KG, int nch);
 hipError_t launch_gemm(const GemmParams& p, int NT, int KG, int wpe, int grid_x, hipStream_t s);
 hipError_t launch_gemm_route(const GemmParams& p, int NT, int KG, int wpe, int grid_x, int route, hipStream_t s);

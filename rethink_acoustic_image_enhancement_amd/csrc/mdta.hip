@@ -659,8 +659,7 @@ static void launch_gram_ct(const GramParams& p, bool generic, hipStream_t s) {
   }
   if constexpr (CT <= 6) {
     if (gram_ring_applies(p)) {
-      const int nseg = p.nslots / (p.W / 16);
-      const int seg_rows = (p.H + nseg - 1) / nseg;
+      const int seg_rows = gram_segments(p.nslots, p.H, p.W).seg_rows;
       if (p.no_v)
         hipLaunchKernelGGL((dwconv_gram_ring_kernel<CT, true>), dim3(p.nslots, p.heads, p.Bn),
                            dim3(64 * gram_ring_waves(CT)), (GramRing<CT, true>::lds_bytes), s, p, seg_rows);
@@ -671,10 +670,9 @@ static void launch_gram_ct(const GramParams& p, bool generic, hipStream_t s) {
     }
   }
   if (p.W % 16 == 0 && p.nslots % (p.W / 16) == 0) {
-    const int nseg = p.nslots / (p.W / 16);
-    const int seg_rows = (p.H + nseg - 1) / nseg;
+    const GramSegs g = gram_segments(p.nslots, p.H, p.W);
     hipLaunchKernelGGL(dwconv_gram_sweep_kernel<CT>, dim3(p.nslots, p.heads, p.Bn), dim3(64 * gram_waves(CT)), 0, s,
-                       p, nseg, seg_rows);
+                       p, g.nseg, g.seg_rows);
   } else {
     hipLaunchKernelGGL(dwconv_gram_kernel<CT>, dim3(p.nslots, p.heads, p.Bn), dim3(256), 0, s, p);
   }

@@ -503,7 +503,7 @@ static hipError_t launch_mdta1(const MdtaFusedParams& p, hipStream_t s) {
 
 hipError_t launch_mdta_fused(const MdtaFusedParams& p, int C, hipStream_t s) {
   if (!mdta_fused_supported(C, 1, p.H, p.W, p.nseg, p.seg_rows) || p.ldx % 4 || p.ldv % 4 || p.Bn <= 0 ||
-      p.nslots != (p.W / 16) * p.nseg || p.slot_floats != (C / 16) * (C / 16) * 256 + 2 * C ||
+      p.nslots != (p.W / 16) * p.nseg || p.slot_floats != gram_slot_floats(C) ||
       (long long)p.H * p.W * std::max(p.ldx, p.ldv) * 4 >= (1LL << 31))
     return hipErrorInvalidValue;
   return C == 48 ? launch_mdta1<48>(p, s) : launch_mdta1<96>(p, s);

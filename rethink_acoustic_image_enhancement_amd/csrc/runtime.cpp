@@ -173,6 +173,124 @@ int run_gemm(const GemmCall& c, hipStream_t s) {
   return KDLAE_OK;
 }
 
+// Which kernel a conv / GEMM layer runs on.  One rule for the three models, merged from the `conv`
+// lambdas of kdlae_s_forward and asdqe_forward and the lds_conv branch of KDLAE-T's Fwd::gemm:
+//   c16   3x3(x3) conv 16 -> 16 channels with a plain store (kgroups = 9 kt, one tile): KDLAE-S kt = 3,
+//         ASDQE kt = 1.  KDLAE-T's 3x3 convs all store through a (un)shuffle map, so none qualifies,
+//         dim = 16 (Downsample 16 -> 8) included.
+//   lds   any other 3x3(x3) conv that conv_lds.hip supports, without residual or LN: the plain store of
+//         KDLAE-S (kt = 3, tap-pair split records w3t) and ASDQE (kt = 1, w3), and KDLAE-T's Downsample
+//         (out_mode 1) and Upsample (out_mode 2) convs (w3, outputs n < n_true only).
+//   gemm  everything else: every 1x1, and 3x3 shapes outside conv_lds_supported.
+constexpr auto KDLAE_T_DOWN_LDS = 1;  // Downsample convs on conv_lds (0: the implicit GEMM)
+constexpr auto KDLAE_T_UP_LDS = 1;  // Upsample convs on conv_lds (0: the implicit GEMM)
+ConvKernel conv_kernel(const Gemm& g, const GemmCall& c) {
+  if (g.ksize != 3 || c.R || c.ln) return ConvKernel::gemm;
+  if (c.out_mode == 0 && g.ntiles == 1 && g.cg_per_tap == 1 && g.kgroups == 9 * g.kt) return ConvKernel::c16;
+  const bool mode_ok = c.out_mode == 0 || (KDLAE_T_DOWN_LDS && c.out_mode == 1) || (KDLAE_T_UP_LDS && c.out_mode == 2);
+  return mode_ok && conv_lds_supported(g.kt, g.ntiles, g.cg_per_tap * 16) ? ConvKernel::lds : ConvKernel::gemm;
+}
+
+int run_conv(const DeviceWeights& D, const Gemm& g, GemmCall c, hipStream_t s) {
+  c.g = &g;
+  c.bias = D.P(g.bias);
+  if (!c.W) c.W = D.P3(g.w3);
+  switch (conv_kernel(g, c)) {
+    case ConvKernel::c16: {  // LDS-tiled kernel with the weights held in VGPRs (conv3d_c16.hip)
+      Conv3dC16Params q{};
+      q.in = c.in.p;
+      q.ldi = c.in.ld;
+      q.wp = D.P(g.w);
+      q.bias = c.bias;
+      q.out = c.out.p;
+      q.ldo = c.out.ld;
+      q.Bn = c.B;
+      q.F = c.F;
+      q.H = c.H;
+      q.W = c.Wd;
+      q.relu = c.relu;
+      q.kt = g.kt;
+      HIPCHK(launch_conv3d_c16(q, s));
+      return KDLAE_OK;
+    }
+    case ConvKernel::lds: {  // LDS-tiled implicit GEMM (conv_lds.hip): halo staged once, no per-tap L1 re-reads
+      ConvLdsParams q{};
+      q.in = c.in.p;
+      q.ldi = c.in.ld;
+      q.cin_pad = g.cg_per_tap * 16;
+      q.wp = D.P(g.w);
+      q.wp3 = g.kt == 3 ? D.P3(g.w3t) : c.W;
+      q.ntiles = g.ntiles;
+      q.kgroups = g.kgroups;
+      q.bias = c.bias;
+      q.out = c.out.p;
+      q.ldo = c.out.ld;
+      q.Bn = c.B;
+      q.F = c.F;
+      q.H = c.H;
+      q.W = c.Wd;
+      q.kt = g.kt;
+      q.relu = c.relu;
+      q.out_mode = c.out_mode;
+      q.nout = c.out_mode ? g.n_true : 0;
+      HIPCHK(launch_conv_lds(q, s));
+      return KDLAE_OK;
+    }
+    case ConvKernel::gemm: break;
+  }
+  return run_gemm(c, s);
+}
+
+// ----------------------------------------------------------------------------- handle lifecycle
+int handle_param_info(const HandleBase* h, int index, const char** name, int64_t* numel) {
+  if (!h) return fail(KDLAE_ESTATE, "null handle");
+  return h->ps.lay.info(index, name, numel, nullptr);
+}
+
+int handle_set_param(HandleBase* h, const char* name, const float* host_data, int64_t numel) {
+  if (!h || !name || !host_data) return fail(KDLAE_ESTATE, "null argument");
+  return h->ps.set(name, host_data, numel);
+}
+
+int handle_prepare(HandleBase* h, RecordFn record) {
+  if (!h) return fail(KDLAE_ESTATE, "null handle");
+  if (h->built) return KDLAE_OK;
+  PackProgram prog;
+  prog.nsrc = h->ps.lay.total;
+  TRY(record(h, prog));
+  DeviceGuard g(h->device);
+  TRY(h->dw.upload_program(prog));
+  h->built = true;
+  return KDLAE_OK;
+}
+
+int handle_commit(HandleBase* h, RecordFn record, void* stream) {
+  if (!h) return fail(KDLAE_ESTATE, "null handle");
+  TRY(h->ps.check_complete());
+  TRY(handle_prepare(h, record));
+  DeviceGuard g(h->device);
+  TRY(h->dw.run_host(h->ps.flat(), reinterpret_cast<hipStream_t>(stream)));
+  h->committed = true;
+  return KDLAE_OK;
+}
+
+int handle_pack_device(HandleBase* h, RecordFn record, const float* params, int64_t numel, void* stream) {
+  if (!h) return fail(KDLAE_ESTATE, "null handle");
+  if (numel != h->ps.lay.total)
+    return fail(KDLAE_EPARAM, "flat parameter vector has " + std::to_string(numel) + " floats, expected " +
+                                  std::to_string(h->ps.lay.total));
+  TRY(handle_prepare(h, record));  // no-op after *_prepare
+  DeviceGuard g(h->device);
+  TRY(h->dw.run(params, reinterpret_cast<hipStream_t>(stream)));
+  h->committed = true;
+  return KDLAE_OK;
+}
+
+void handle_release(HandleBase* h) {
+  DeviceGuard g(h->device);
+  h->dw.release();
+}
+
 int device_cu_count() {
   static std::mutex mu;
   static std::map<int, int> per_device;  // a process may drive several GPUs (nn.DataParallel-style)

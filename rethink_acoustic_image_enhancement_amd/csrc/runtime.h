@@ -1,5 +1,6 @@
 // Shared host runtime for the KDLAE-T / KDLAE-S / ASDQE handles: error state, packed-weight
-// descriptors, GEMM tile-variant selection, the weight arena and a GEMM launcher over NHWC views.
+// descriptors, GEMM tile-variant selection, the weight arena, the handles' parameter lifecycle and the
+// GEMM / conv launchers over NHWC views.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,6 +14,7 @@
 #include "../../include/kdlae.h"
 #include "kernels.h"
 #include "mfma3.h"
+#include "param_layout.h"
 
 namespace kdlae {
 
@@ -154,6 +156,25 @@ struct DeviceWeights {
   const float* P3(size_t off) const { return off == kNone ? nullptr : dev3 + off; }
 };
 
+// What the three inference handles share: kdlae_t_handle, kdlae_s_handle and asdqe_handle derive from
+// it and their parameter entry points are the handle_* functions below (null handle: KDLAE_ESTATE).
+struct HandleBase {
+  int device = 0;
+  ParamStore ps;           // expected state_dict keys (ordered, flat offsets) + host-staged values
+  bool built = false;      // pack program uploaded (depends on the config only)
+  bool committed = false;  // arena filled from parameters at least once
+  DeviceWeights dw;        // packed arena + the pack program that fills it from the parameters
+};
+// A model's program builder: records the packed layout of the handle's configuration into `prog`
+// (and the offsets into the handle).  Runs once per handle, on the first prepare / commit / pack.
+using RecordFn = int (*)(HandleBase* h, PackProgram& prog);
+int handle_param_info(const HandleBase* h, int index, const char** name, int64_t* numel);
+int handle_set_param(HandleBase* h, const char* name, const float* host_data, int64_t numel);
+int handle_prepare(HandleBase* h, RecordFn record);
+int handle_commit(HandleBase* h, RecordFn record, void* stream);
+int handle_pack_device(HandleBase* h, RecordFn record, const float* params, int64_t numel, void* stream);
+void handle_release(HandleBase* h);  // the device side; the caller deletes the handle
+
 // Restores the caller's current device when it goes out of scope.
 struct DeviceGuard {
   int prev = -1;
@@ -203,10 +224,19 @@ struct GemmCall {
   View out1{nullptr, 0};
 };
 int run_gemm(const GemmCall& c, hipStream_t s);
+// One conv / GEMM layer on the kernel that suits it: exactly one launch of launch_conv3d_c16,
+// launch_conv_lds or run_gemm (the rule is written down at conv_kernel in runtime.cpp).  Fills c.g,
+// c.bias and, unless the caller set per-image weights, c.W from the handle's arenas.
+enum class ConvKernel { c16, lds, gemm };
+ConvKernel conv_kernel(const Gemm& g, const GemmCall& c);
+int run_conv(const DeviceWeights& D, const Gemm& g, GemmCall c, hipStream_t s);
 // Compute units of the current device (256 on MI355X) and the tail-aware GEMM grid split.
 int device_cu_count();  // of the current device
 int gemm_tiles_per_block(int total_tiles, int gy, bool resident, int wpe);
 // Partial Gram slots per (image, head) of the KDLAE-T attention at image size H x W (kdlae_t.cpp)
 int nslots_for(int H, int W);
+// Floats per image of the attention's folded projection M = W_proj . softmax(...) of a C-channel block,
+// in split fragment order (launch_attn_fold writes it, the attention-output kernels read it)
+inline long long folded_proj_floats(int C) { return split3_floats(C / 16, C / 16); }
 
 }  // namespace kdlae

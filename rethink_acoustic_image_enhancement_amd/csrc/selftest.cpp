@@ -185,8 +185,7 @@ extern "C" int kdlae_debug_gram(const kdlae_debug_gram_desc* d, void* stream) {
   p.H = d->H;
   p.W = d->W;
   p.nslots = kdlae::nslots_for(d->H, d->W);  // the engine's slot count
-  const int CT = p.Ch / 16;
-  p.slot_floats = CT * CT * 256 + 2 * p.Ch;
+  p.slot_floats = kdlae::gram_slot_floats(p.Ch);
   p.zeros = (d->route == 0 || no_v) ? d->zeros : nullptr;
   p.no_v = no_v ? 1 : 0;
   if ((long long)d->Bn * d->heads * p.nslots * p.slot_floats > d->partial_floats)
@@ -690,7 +689,7 @@ extern "C" int kdlae_debug_infer(const kdlae_debug_infer_desc* d, void* stream) 
         return fail(KDLAE_EINVAL_SHAPE, bad);
       if (!in4(0) || !out4(0) || !al16(d->w[1]) || !al16(d->bias[0]) || !al16(d->bias[1]) || !al16(d->scratch))
         return fail(KDLAE_EINVAL_SHAPE, align);
-      const int CT = C / 16, nslots = (d->W / 16) * d->nseg, slot_floats = CT * CT * 256 + 2 * C;
+      const int nslots = (d->W / 16) * d->nseg, slot_floats = kdlae::gram_slot_floats(C);
       if ((long long)d->Bn * nslots * slot_floats > d->scratch_floats)
         return fail(KDLAE_EINVAL_SHAPE, "scratch must hold Bn * nslots * slot_floats floats");
       HIPCHK(sc.split(0, d->w[0], 3 * C / 16, C / 16));
@@ -708,8 +707,7 @@ extern "C" int kdlae_debug_infer(const kdlae_debug_infer_desc* d, void* stream) 
       if (d->heads < 1 || C < 16 || C % 16 || C % d->heads || (C / d->heads) % 16 || C / d->heads > 128 || d->Bn < 1 ||
           d->Bn > 65535 || d->heads > 65535)
         return fail(KDLAE_EINVAL_SHAPE, "attn_fold: C = heads * Ch, Ch a multiple of 16, 16 .. 128");
-      const int Ch = C / d->heads, CT = Ch / 16;
-      e = kdlae::launch_attn_fold(d->in[0], CT * CT * 256 + 2 * Ch, d->w[0], d->w[1], d->out[0], d->Bn, C, d->heads, s);
+      e = kdlae::launch_attn_fold(d->in[0], kdlae::gram_slot_floats(C / d->heads), d->w[0], d->w[1], d->out[0], d->Bn, C, d->heads, s);
       break;
     }
     case 4: {  // GDFN dwconv + gate
@@ -831,7 +829,7 @@ extern "C" int kdlae_debug_infer(const kdlae_debug_infer_desc* d, void* stream) 
       }
       kdlae::AttnOutDwParams p{};
       p.v = d->in[0]; p.ldv = d->ldi[0]; p.wdw = d->w[0] + 2 * C; p.ldw = 3 * C; p.bdw = d->bias[0] ? d->bias[0] + 2 * C : nullptr;
-      p.M = d->w[1]; p.m_img_stride = kdlae::split3_floats(C / 16, C / 16); p.bias = d->bias[1];
+      p.M = d->w[1]; p.m_img_stride = kdlae::folded_proj_floats(C); p.bias = d->bias[1];
       p.R = d->R; p.ldr = d->ldr; p.out = d->out[0]; p.ldo = d->ldo[0];
       p.Bn = d->Bn; p.H = d->H; p.W = d->W; p.zeros = d->zeros;
       e = kdlae::launch_attn_out_dw(p, C, s);

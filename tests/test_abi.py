@@ -57,6 +57,50 @@ def test_param_enumeration_matches_module_state_dict(kw):
     L.kdlae_t_destroy(h)
 
 
+# KDLAE_teacher.forward's TransformerBlock stages in the order it runs them (KDLAE_model.py:275-329), each
+# with the resolution it runs at relative to the input: three PixelUnshuffle(2) levels down, back up, and
+# the sr head's `enhance` behind a PixelShuffle(2)
+_FORWARD_STAGES = [("encoder_level1", 1, 1), ("encoder_level2", 1, 2), ("encoder_level3", 1, 4), ("latent", 1, 8),
+                   ("decoder_level3", 1, 4), ("decoder_level2", 1, 2), ("decoder_level1", 1, 1), ("refinement", 1, 1),
+                   ("refinement_out", 1, 1), ("enhance", 2, 1)]
+
+
+@pytest.mark.parametrize("kw", [dict(LayerNorm_type="BiasFree"), dict(), dict(bias=True, static="no", params="plus"),
+                                dict(dim=16, inp_channels=1, out_channels=1, num_blocks=[1, 2, 1, 1]),
+                                dict(params="plus"), dict(static="no"),
+                                dict(dim=16, num_blocks=[1, 0, 2, 1], num_refinement_blocks=1),
+                                dict(dim=16, num_blocks=[0, 1, 1, 0], static="no", params="plus")])
+def test_debug_taps_follow_the_module_stages(kw):
+    """kdlae_t_debug_tap_count / _info list, per stage the module's forward runs, `<stage>.in`, then per block
+    `<stage>.<i>.attn` and `<stage>.<i>`, with the stage's channel count and resolution ratio.  The expected
+    list comes from the Python module (its Sequential lengths and LayerNorm widths), not from the library."""
+    m = KDLAE_teacher(**kw)
+    expected = []
+    for stage, num, den in _FORWARD_STAGES:
+        if stage == "refinement_out" and m.params != "cat":
+            continue
+        if stage == "enhance" and m.static != "train":
+            continue
+        blocks = getattr(m, stage)
+        if len(blocks) == 0:
+            continue
+        C = blocks[0].norm1.body.weight.numel()
+        expected.append((f"{stage}.in", C, num, den))
+        for i in range(len(blocks)):
+            expected += [(f"{stage}.{i}.attn", C, num, den), (f"{stage}.{i}", C, num, den)]
+    rc, h = _create(m)
+    assert rc == 0, _lib.last_error()
+    L = _lib.lib()
+    got = []
+    for i in range(L.kdlae_t_debug_tap_count(h)):
+        name, C, num, den = ctypes.create_string_buffer(64), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        assert L.kdlae_t_debug_tap_info(h, i, name, 64, ctypes.byref(C), ctypes.byref(num), ctypes.byref(den)) == 0
+        got.append((name.value.decode(), C.value, num.value, den.value))
+    assert got == expected
+    assert L.kdlae_t_debug_tap_info(h, len(got), None, 0, None, None, None) == 4   # index out of range
+    L.kdlae_t_destroy(h)
+
+
 def test_config_validation_errors():
     rc, h = _create(KDLAE_teacher(dim=16, dual_pixel_task=True))
     assert rc == 5 and "NameError" in _lib.last_error()
