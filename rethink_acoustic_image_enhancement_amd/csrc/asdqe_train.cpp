@@ -26,22 +26,18 @@
 #include "param_layout.h"
 #include "runtime.h"
 #include "train_a.h"
+#include "train_host.h"
 #include "train_kernels.h"
 #include "train_s.h"
 
 using namespace kdlae;
 namespace tr = kdlae::train;
 
-struct asdqe_train_handle {
+struct asdqe_train_handle : TrainHandleBase {  // lay: named_parameters() order
   asdqe_config cfg{};
-  int device = 0;
-  ParamLayout lay{4};  // named_parameters() order, every key 16-byte aligned
-  int64_t nstat = 0;   // floats of the statistics buffer: every BatchNorm's running_mean | running_var
-  // the last forward (its activations live in the caller's workspace)
-  bool valid = false;
-  int B = 0, H = 0, W = 0;
-  bool has_m1 = false, has_m2 = false;
-  const void* ws = nullptr;
+  int64_t nstat = 0;  // floats of the statistics buffer: every BatchNorm's running_mean | running_var
+  LastForward last;
+  bool has_m1 = false, has_m2 = false;  // the last forward had dropout masks
 };
 
 namespace {
@@ -154,24 +150,20 @@ TPlan make_plan(const asdqe_train_handle* h, int B, int H, int W) {
   return pl;
 }
 
-struct Ctx {
+// gr: the backward's own gradient buffer (workspace), committed to the caller's at the end
+struct Ctx : FlatCtx {
   asdqe_train_handle* h;
-  const float* th;
-  float* gr;  // the backward's own gradient buffer (workspace), committed to the caller's at the end
-  char* ws;
   TPlan pl;
   hipStream_t s;
   int B;
-  float* buf(size_t o) const { return reinterpret_cast<float*>(ws + o); }
-  const float* P(const std::string& k) const { return th + h->lay.at(k); }
-  float* G(const std::string& k) const { return gr + h->lay.at(k); }
 };
 
-// the implicit-GEMM 3x3 conv's B operand as a [9 Cg][N] matrix (bmode 2 / 3 -> 0)
-int pack_w3(Ctx& c, tr::TGemm& g, int N) {
-  float* wp = c.buf(c.pl.wpk);
-  HIPCHK(tr::launch_pack_w3(g.B, g.Cg, N, g.bmode, wp, c.s));
-  tr::use_packed_w3(g, wp, N);
+// one of a conv layer's three GEMMs: the 3x3 weight operand (bmode 2 / 3) repacked into the fixed wpk
+// buffer as a [9 Cg][N] matrix, split-K partials from the plan
+int conv_gemm(Ctx& c, tr::TGemm g, bool pack) {
+  if (pack) HIPCHK(tr::launch_pack_w3(g, g.N, c.buf(c.pl.wpk), c.s));
+  g.partial = c.buf(c.pl.partial);
+  HIPCHK(tr::launch_tgemm(g, kPartialFloats, c.s));
   return KDLAE_OK;
 }
 
@@ -205,16 +197,8 @@ int layer_fwd(Ctx& c, const Layer& L, const float* lq, const float* gt, int H, i
     p.relu = 0;
     HIPCHK(launch_conv_small_in(p, c.s));
   } else {
-    tr::TGemm g;
-    g.A = c.buf(L.in); g.amode = 1; g.lda = L.in_ld; g.Cg = L.cin;
-    g.B = c.P(L.cv + ".weight"); g.bmode = 2;
-    TRY(pack_w3(c, g, L.cout));
-    g.C = z; g.scm = L.z_ld; g.scn = 1;
-    g.bias = c.P(L.cv + ".bias");
-    g.M = (int)P; g.N = L.cout; g.K = 9 * L.cin;
-    g.Bn = c.B; g.H = Hl; g.W = Wl; g.dil = 1;
-    g.partial = c.buf(c.pl.partial);
-    HIPCHK(tr::launch_tgemm(g, kPartialFloats, c.s));
+    TRY(conv_gemm(c, tr::conv3_fwd_gemm({c.buf(L.in), L.in_ld, L.cin}, c.P(L.cv + ".weight"), c.P(L.cv + ".bias"),
+                                        {z, L.z_ld, L.cout}, {c.B, Hl, Wl, 1}), true));
   }
   float* ms = c.buf(L.ms);
   HIPCHK(tr::launch_bn_stats(z, L.z_ld, L.cout, P, ms, ms + L.cout, stats + L.run, stats + L.run + L.cout, kMomentum,
@@ -253,28 +237,9 @@ int layer_bwd(Ctx& c, const Layer& L, float* dy, int ldd, float* dx, int lddx) {
     }
     return KDLAE_OK;
   }
-  {
-    tr::TGemm g;  // dW[co][ci][t] = sum_p dz[p, co] x[p + off_t, ci]
-    g.A = dy; g.sam = 1; g.sak = ldd;
-    g.B = c.buf(L.in); g.bmode = 1; g.ldb = L.in_ld;
-    g.C = gw; g.scm = (long long)L.cin * 9; g.scn = 9; g.bC2 = 1;
-    g.nz2 = 9;
-    g.M = L.cout; g.N = L.cin; g.K = (int)P;
-    g.Bn = c.B; g.H = Hl; g.W = Wl; g.dil = 1;
-    g.partial = c.buf(c.pl.partial);
-    HIPCHK(tr::launch_tgemm(g, kPartialFloats, c.s));
-  }
-  if (dx) {
-    tr::TGemm d;  // the transposed conv: flipped taps, channels swapped
-    d.A = dy; d.amode = 1; d.lda = ldd; d.Cg = L.cout;
-    d.B = c.P(L.cv + ".weight"); d.bmode = 3;
-    TRY(pack_w3(c, d, L.cin));
-    d.C = dx; d.scm = lddx; d.scn = 1;
-    d.M = (int)P; d.N = L.cin; d.K = 9 * L.cout;
-    d.Bn = c.B; d.H = Hl; d.W = Wl; d.dil = 1;
-    d.partial = c.buf(c.pl.partial);
-    HIPCHK(tr::launch_tgemm(d, kPartialFloats, c.s));
-  }
+  const tr::ConvGeo geo{c.B, Hl, Wl, 1};
+  TRY(conv_gemm(c, tr::conv3_dw_gemm({dy, ldd, L.cout}, {c.buf(L.in), L.in_ld, L.cin}, gw, geo), false));
+  if (dx) TRY(conv_gemm(c, tr::conv3_dx_gemm({dy, ldd, L.cout}, c.P(L.cv + ".weight"), {dx, lddx, L.cin}, geo), true));
   return KDLAE_OK;
 }
 
@@ -402,6 +367,7 @@ int check_shape(int B, const TPlan& pl) {
 
 extern "C" {
 
+// asdqe_train_* report a null argument as KDLAE_ESTATE (kdlae_tt_*: KDLAE_EINVAL_CONFIG)
 int asdqe_train_create(const asdqe_config* cfg, int device, asdqe_train_handle** out) {
   if (!cfg || !out) return fail(KDLAE_ESTATE, "null argument");
   *out = nullptr;
@@ -417,19 +383,15 @@ int asdqe_train_create(const asdqe_config* cfg, int device, asdqe_train_handle**
   return KDLAE_OK;
 }
 
-int asdqe_train_destroy(asdqe_train_handle* h) {
-  delete h;
-  return KDLAE_OK;
-}
+int asdqe_train_destroy(asdqe_train_handle* h) { return train_destroy(h); }
 
-int asdqe_train_num_params(const asdqe_train_handle* h) { return h ? h->lay.size() : -1; }
+int asdqe_train_num_params(const asdqe_train_handle* h) { return train_num_params(h, -1); }
 
 int asdqe_train_param_info(const asdqe_train_handle* h, int i, const char** name, int64_t* numel, int64_t* offset) {
-  if (!h) return fail(KDLAE_EPARAM, "param index out of range");
-  return h->lay.info(i, name, numel, offset);
+  return train_param_info(h, i, name, numel, offset);
 }
 
-int64_t asdqe_train_num_floats(const asdqe_train_handle* h) { return h ? h->lay.total : -1; }
+int64_t asdqe_train_num_floats(const asdqe_train_handle* h) { return train_num_floats(h); }
 int64_t asdqe_train_num_stat_floats(const asdqe_train_handle* h) { return h ? h->nstat : -1; }
 
 int64_t asdqe_train_workspace_bytes(const asdqe_train_handle* h, int B, int H, int W) {
@@ -448,13 +410,14 @@ int asdqe_train_forward(asdqe_train_handle* h, const float* theta, float* stats,
                         int64_t workspace_bytes, void* stream) {
   if (!h || !theta || !stats || !lq || !gt || !score || !workspace) return fail(KDLAE_ESTATE, "null argument");
   if (B <= 0 || H <= 0 || W <= 0) return fail(KDLAE_EINVAL_SHAPE, "B, H, W must be positive");
-  Ctx c{h, theta, nullptr, reinterpret_cast<char*>(workspace), make_plan(h, B, H, W), (hipStream_t)stream, B};
+  Ctx c{{&h->lay, theta, nullptr, reinterpret_cast<char*>(workspace)}, h, make_plan(h, B, H, W), (hipStream_t)stream,
+        B};
   TRY(check_shape(B, c.pl));
   if ((int64_t)c.pl.total > workspace_bytes) return fail(KDLAE_ESTATE, "training workspace too small");
   if (((uintptr_t)theta | (uintptr_t)stats | (uintptr_t)workspace) & 15)
     return fail(KDLAE_ESTATE, "theta, stats and the workspace must be 16-byte aligned");
   DeviceGuard dg(h->device);
-  h->valid = false;
+  h->last.valid = false;
   h->has_m1 = mask1 != nullptr;
   h->has_m2 = mask2 != nullptr;
   if (mask1)
@@ -462,38 +425,25 @@ int asdqe_train_forward(asdqe_train_handle* h, const float* theta, float* stats,
   if (mask2)
     HIPCHK(hipMemcpyAsync(c.buf(c.pl.m2), mask2, (size_t)B * kN2 * sizeof(float), hipMemcpyDeviceToDevice, c.s));
   TRY(net_fwd(c, lq, gt, H, W, stats, score));
-  h->valid = true;
-  h->B = B;
-  h->H = H;
-  h->W = W;
-  h->ws = workspace;
+  h->last.set(workspace, B, 1, H, W);
   return KDLAE_OK;
 }
 
 int asdqe_train_backward(asdqe_train_handle* h, const float* theta, const float* dscore, float* grad, int accumulate,
                          void* workspace, int64_t workspace_bytes, void* stream) {
   if (!h || !theta || !dscore || !grad || !workspace) return fail(KDLAE_ESTATE, "null argument");
-  if (!h->valid || h->ws != workspace)
-    return fail(KDLAE_ESTATE, "asdqe_train_backward needs a preceding asdqe_train_forward on the same workspace");
-  Ctx c{h, theta, nullptr, reinterpret_cast<char*>(workspace), make_plan(h, h->B, h->H, h->W), (hipStream_t)stream,
-        h->B};
+  TRY(h->last.check(workspace, "asdqe_train_backward", "asdqe_train_forward"));
+  Ctx c{{&h->lay, theta, nullptr, reinterpret_cast<char*>(workspace)}, h, make_plan(h, h->last.B, h->last.H, h->last.W),
+        (hipStream_t)stream, h->last.B};
   if ((int64_t)c.pl.total > workspace_bytes) return fail(KDLAE_ESTATE, "training workspace too small");
   if (((uintptr_t)theta | (uintptr_t)grad) & 15) return fail(KDLAE_ESTATE, "theta and grad must be 16-byte aligned");
   DeviceGuard dg(h->device);
   c.gr = c.buf(c.pl.gtmp);
   // zero: the pad floats and the BatchNorm-fed conv biases, whose gradient is exactly zero
   HIPCHK(hipMemsetAsync(c.gr, 0, (size_t)h->lay.total * sizeof(float), c.s));
-  h->valid = false;  // a forward's activations serve one backward
+  h->last.valid = false;  // a forward's activations serve one backward
   TRY(net_bwd(c, dscore));
   HIPCHK(tr::launch_grad_commit(c.gr, grad, h->lay.total, accumulate ? 1 : 0, c.s));
-  return KDLAE_OK;
-}
-
-int kdlae_train_mse(const float* score, const float* target, int n, float scale, float* dscore, float* loss,
-                    void* stream) {
-  if (!score || !target || !dscore || !loss) return fail(KDLAE_ESTATE, "null argument");
-  if (n <= 0) return fail(KDLAE_EINVAL_SHAPE, "empty loss input");
-  HIPCHK(tr::launch_mse(score, target, n, scale, dscore, loss, (hipStream_t)stream));
   return KDLAE_OK;
 }
 

@@ -15,39 +15,26 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
-#include <tuple>
 #include <unordered_map>
 #include <vector>
 
 #include "kernels.h"
 #include "param_layout.h"
 #include "runtime.h"
+#include "train_host.h"
 #include "train_kernels.h"
 #include "train_s.h"
 
 using namespace kdlae;
 namespace tr = kdlae::train;
 
-struct kdlae_st_handle {
+struct kdlae_st_handle : TrainHandleBase {
   kdlae_s_config cfg{};
-  int device = 0;
   int L = 0;
   std::vector<int> hc;
-  ParamLayout lay{4};  // state_dict order, every key 16-byte aligned
-  // the last forward (its activations live in the caller's workspace)
-  bool valid = false;
-  int B = 0, F = 0, H = 0, W = 0;
-  const void* ws = nullptr;
-  const float* x = nullptr;
-  // backward side stream (non-blocking) for the Conv3d weight / bias gradients, and its fork / join
-  // events (KDLAE_DEBUG=train_serial: everything on the caller's stream)
-  hipStream_t side = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  ~kdlae_st_handle() {
-    if (ev_fork) (void)hipEventDestroy(ev_fork);
-    if (ev_join) (void)hipEventDestroy(ev_join);
-    if (side) (void)hipStreamDestroy(side);
-  }
+  LastForward last;
+  const float* x = nullptr;  // the last forward's input
+  SideStream side;           // the backward's: the Conv3d weight / bias gradients run there
 };
 
 namespace {
@@ -82,6 +69,24 @@ bool dx_direct(int cin, int cout) {
          ((cin == 16 && cout == 16) || conv_lds_supported(3, cin / 16, cout));
 }
 
+// the net's Conv3d layers in forward order
+struct ConvLayer {
+  std::string name;
+  int cin, cout, lvl;
+};
+std::vector<ConvLayer> conv_layers(const kdlae_st_handle* h) {
+  const int L = h->L;
+  std::vector<ConvLayer> v;
+  auto pair = [&](const std::string& p, int cin, int c, int lvl) {
+    v.push_back({p + ".0", cin, c, lvl});
+    v.push_back({p + ".2", c, c, lvl});
+  };
+  for (int i = 0; i < L; ++i) pair("encoders." + std::to_string(i), i ? h->hc[i - 1] : 1, h->hc[i], i);
+  pair("st_fusion", h->hc[L - 1], h->hc[L], L);
+  for (int j = 0; j < L; ++j) pair("decoders." + std::to_string(j), h->hc[L - 1 - j], h->hc[L - 1 - j], L - 1 - j);
+  return v;
+}
+
 SPlanT make_plan(const kdlae_st_handle* h, int B, int F, int H, int W) {
   SPlanT pl;
   const int L = h->L;
@@ -108,25 +113,10 @@ SPlanT make_plan(const kdlae_st_handle* h, int B, int F, int H, int W) {
     pl.da.push_back(pl.take(P * c));
     pl.dl.push_back(pl.take(P * c));
   }
-  // per Conv3d (name, input channels, output channels, level): its Xcol (only for the convs that are
-  // not direct) is kept from the forward for its weight gradient
-  std::vector<std::tuple<std::string, int, int, int>> convs;
-  for (int i = 0; i < L; ++i) {
-    const std::string p = "encoders." + std::to_string(i);
-    convs.emplace_back(p + ".0", i ? h->hc[i - 1] : 1, h->hc[i], i);
-    convs.emplace_back(p + ".2", h->hc[i], h->hc[i], i);
-  }
-  convs.emplace_back("st_fusion.0", h->hc[L - 1], h->hc[L], L);
-  convs.emplace_back("st_fusion.2", h->hc[L], h->hc[L], L);
-  for (int j = 0; j < L; ++j) {
-    const int i = L - 1 - j;
-    const std::string d = "decoders." + std::to_string(j);
-    convs.emplace_back(d + ".0", h->hc[i], h->hc[i], i);
-    convs.emplace_back(d + ".2", h->hc[i], h->hc[i], i);
-  }
-  // scratch: the dX columns of the convs whose dX is not direct, and the ConvTranspose dU
+  // scratch: the dX columns of the convs whose dX is not direct, and the ConvTranspose dU; per Conv3d
+  // that is not direct, its Xcol, kept from the forward for its weight gradient
   for (int i = 0; i < L; ++i) colmax = std::max(colmax, npx(h, i, B, F, H, W) * h->hc[i]);
-  for (auto& [name, ci, co, lvl] : convs) {
+  for (const auto& [name, ci, co, lvl] : conv_layers(h)) {
     const long long P = npx(h, lvl, B, F, H, W);
     if (!dx_direct(ci, co)) {
       colmax = std::max(colmax, P * 27 * ci);
@@ -148,19 +138,13 @@ SPlanT make_plan(const kdlae_st_handle* h, int B, int F, int H, int W) {
   return pl;
 }
 
-struct Ctx {
+struct Ctx : FlatCtx {
   kdlae_st_handle* h;
-  const float* th;
-  float* gr;
-  char* ws;
   SPlanT pl;
   hipStream_t s;
   int B, F, H, W;
-  hipStream_t side = nullptr;    // set by the backward unless KDLAE_DEBUG=train_serial
+  SideStream* side = nullptr;    // set by the backward unless KDLAE_DEBUG=train_serial
   hipStream_t main_s = nullptr;  // the caller's stream (c.s is the side stream inside a side segment)
-  float* buf(size_t o) const { return reinterpret_cast<float*>(ws + o); }
-  const float* P(const std::string& k) const { return th + h->lay.at(k); }
-  float* G(const std::string& k) const { return gr + h->lay.at(k); }
 };
 
 int gemm(Ctx& c, tr::TGemm g, bool split) {
@@ -182,34 +166,41 @@ int colsum(Ctx& c, const float* x, int ld, int ncols, long long rows, float* out
   return KDLAE_OK;
 }
 
+// Conv3d p (cin -> cout channels) at level lvl on the inference kernels, conv3d_c16 for 16 -> 16 and
+// conv_lds for 2..16 output tiles, from the weight packed into wpk.  grad 0: the forward, out =
+// relu(conv(in) + b).  grad 1: the input gradient, out = the conv of in = dZ with flipped taps (cout ->
+// cin channels), no ReLU; no bias, which conv3d_c16 takes as a zero vector and conv_lds as null.
+int conv_packed(Ctx& c, const std::string& p, int cin, int cout, int lvl, int grad, const float* in, float* out) {
+  const int ci = grad ? cout : cin, co = grad ? cin : cout, Hl = c.H >> lvl, Wl = c.W >> lvl;
+  float* wpk = c.buf(c.pl.wpk);
+  HIPCHK(tr::launch_pack_conv(c.P(p + ".weight"), cout, cin, grad, wpk, c.s));
+  if (ci == 16 && co == 16) {
+    Conv3dC16Params q{};
+    q.in = in; q.ldi = ci;
+    q.wp = wpk; q.bias = grad ? c.buf(c.pl.zb) : c.P(p + ".bias");
+    q.out = out; q.ldo = co;
+    q.Bn = c.B; q.F = c.F; q.H = Hl; q.W = Wl;
+    q.relu = !grad; q.kt = 3;
+    HIPCHK(launch_conv3d_c16(q, c.s));
+  } else {
+    ConvLdsParams q{};
+    q.in = in; q.ldi = ci; q.cin_pad = ci;
+    q.wp = wpk; q.ntiles = co / 16; q.kgroups = 27 * ci / 16;
+    q.bias = grad ? nullptr : c.P(p + ".bias");
+    q.out = out; q.ldo = co;
+    q.Bn = c.B; q.F = c.F; q.H = Hl; q.W = Wl;
+    q.kt = 3; q.relu = !grad;
+    HIPCHK(launch_conv_lds(q, c.s));
+  }
+  return KDLAE_OK;
+}
+
 // Y = relu(conv(X, W) + b) on the inference kernels (conv_direct) or as Xcol . W'^T + b (W' = the weight
 // in the columns' tap-major order) over P pixels at level lvl
 int conv_fwd(Ctx& c, const std::string& p, const float* X, int cin, float* Y, int cout, int lvl) {
   const int Hl = c.H >> lvl, Wl = c.W >> lvl;
   const long long P = (long long)c.B * c.F * Hl * Wl;
-  if (conv_direct(cin, cout, Wl)) {
-    float* wpk = c.buf(c.pl.wpk);
-    HIPCHK(tr::launch_pack_conv(c.P(p + ".weight"), cout, cin, 0, wpk, c.s));
-    if (cin == 16 && cout == 16) {
-      Conv3dC16Params q{};
-      q.in = X; q.ldi = cin;
-      q.wp = wpk; q.bias = c.P(p + ".bias");
-      q.out = Y; q.ldo = cout;
-      q.Bn = c.B; q.F = c.F; q.H = Hl; q.W = Wl;
-      q.relu = 1; q.kt = 3;
-      HIPCHK(launch_conv3d_c16(q, c.s));
-    } else {
-      ConvLdsParams q{};
-      q.in = X; q.ldi = cin; q.cin_pad = cin;
-      q.wp = wpk; q.ntiles = cout / 16; q.kgroups = 27 * cin / 16;
-      q.bias = c.P(p + ".bias");
-      q.out = Y; q.ldo = cout;
-      q.Bn = c.B; q.F = c.F; q.H = Hl; q.W = Wl;
-      q.kt = 3; q.relu = 1;
-      HIPCHK(launch_conv_lds(q, c.s));
-    }
-    return KDLAE_OK;
-  }
+  if (conv_direct(cin, cout, Wl)) return conv_packed(c, p, cin, cout, lvl, 0, X, Y);
   float* col = c.buf(c.pl.xcol.at(p));
   float* wp = c.buf(c.pl.wp);
   HIPCHK(tr::launch_wperm(c.P(p + ".weight"), wp, cout, cin, 0, c.s));
@@ -226,20 +217,16 @@ int conv_fwd(Ctx& c, const std::string& p, const float* X, int cin, float* Y, in
 }
 
 // the side stream waits for the main stream's current point; launches then go to the side stream
-int side_fork(Ctx& c, hipStream_t main_s) {
+int side_fork(Ctx& c) {
   if (!c.side) return KDLAE_OK;
-  HIPCHK(hipEventRecord(c.h->ev_fork, main_s));
-  HIPCHK(hipStreamWaitEvent(c.side, c.h->ev_fork, 0));
-  c.s = c.side;
+  TRY(c.side->fork(c.main_s));
+  c.s = c.side->s;
   return KDLAE_OK;
 }
 // back to the main stream, which waits for the side stream's launches
-int side_join(Ctx& c, hipStream_t main_s) {
-  c.s = main_s;
-  if (!c.side) return KDLAE_OK;
-  HIPCHK(hipEventRecord(c.h->ev_join, c.side));
-  HIPCHK(hipStreamWaitEvent(main_s, c.h->ev_join, 0));
-  return KDLAE_OK;
+int side_join(Ctx& c) {
+  c.s = c.main_s;
+  return c.side ? c.side->join(c.main_s) : KDLAE_OK;
 }
 
 // dY (grad of the ReLU output Y) -> weight / bias gradients and, when dX != null, the input gradient.
@@ -250,7 +237,7 @@ int conv_bwd_body(Ctx& c, const std::string& p, const float* X, int cin, const f
   const int Hl = c.H >> lvl, Wl = c.W >> lvl;
   const long long P = (long long)c.B * c.F * Hl * Wl;
   HIPCHK(tr::launch_relu_mask(dY, cout, Y, cout, cout, P, c.s));
-  TRY(side_fork(c, c.main_s));
+  TRY(side_fork(c));
   TRY(colsum(c, dY, cout, cout, P, c.G(p + ".bias")));
   float* col = c.buf(c.pl.col);
   float* wp = c.buf(c.pl.wp);
@@ -273,29 +260,7 @@ int conv_bwd_body(Ctx& c, const std::string& p, const float* X, int cin, const f
   if (!dX) return KDLAE_OK;
   // dX = the forward conv of dZ with flipped taps (cout -> cin channels) on the inference kernels:
   // conv3d_c16 for 16 -> 16, conv_lds for 2..16 output tiles; no column matrix, no col2im
-  if (dx_direct(cin, cout)) {
-    float* wpk = c.buf(c.pl.wpk);
-    HIPCHK(tr::launch_pack_conv(c.P(p + ".weight"), cout, cin, 1, wpk, c.s));
-    if (cin == 16 && cout == 16) {
-      Conv3dC16Params q{};
-      q.in = dY; q.ldi = cout;
-      q.wp = wpk; q.bias = c.buf(c.pl.zb);
-      q.out = dX; q.ldo = cin;
-      q.Bn = c.B; q.F = c.F; q.H = Hl; q.W = Wl;
-      q.relu = 0; q.kt = 3;
-      HIPCHK(launch_conv3d_c16(q, c.s));
-    } else {
-      ConvLdsParams q{};
-      q.in = dY; q.ldi = cout; q.cin_pad = cout;
-      q.wp = wpk; q.ntiles = cin / 16; q.kgroups = 27 * cout / 16;
-      q.bias = nullptr;
-      q.out = dX; q.ldo = cin;
-      q.Bn = c.B; q.F = c.F; q.H = Hl; q.W = Wl;
-      q.kt = 3; q.relu = 0;
-      HIPCHK(launch_conv_lds(q, c.s));
-    }
-    return KDLAE_OK;
-  }
+  if (dx_direct(cin, cout)) return conv_packed(c, p, cin, cout, lvl, 1, dY, dX);
   HIPCHK(tr::launch_wperm(c.P(p + ".weight"), wp, cout, cin, 0, c.s));
   tr::TGemm d;  // dXcol = dZ . W', then the gather
   d.A = dY; d.sam = cout; d.sak = 1;
@@ -310,7 +275,7 @@ int conv_bwd_body(Ctx& c, const std::string& p, const float* X, int cin, const f
 int conv_bwd(Ctx& c, const std::string& p, const float* X, int cin, const float* Y, float* dY, int cout, int lvl,
              float* dX) {
   const int r = conv_bwd_body(c, p, X, cin, Y, dY, cout, lvl, dX);
-  const int j = side_join(c, c.main_s);  // also on an error path: no side launch left unjoined
+  const int j = side_join(c);  // also on an error path: no side launch left unjoined
   return r ? r : j;
 }
 
@@ -436,6 +401,7 @@ int net_bwd(Ctx& c, const float* x, const float* dout) {
 
 extern "C" {
 
+// kdlae_st_* report a null argument as KDLAE_ESTATE (kdlae_tt_*: KDLAE_EINVAL_CONFIG)
 int kdlae_st_create(const kdlae_s_config* cfg, int device, kdlae_st_handle** out) {
   if (!cfg || !out) return fail(KDLAE_ESTATE, "null argument");
   *out = nullptr;
@@ -464,19 +430,15 @@ int kdlae_st_create(const kdlae_s_config* cfg, int device, kdlae_st_handle** out
   return KDLAE_OK;
 }
 
-int kdlae_st_destroy(kdlae_st_handle* h) {
-  delete h;
-  return KDLAE_OK;
-}
+int kdlae_st_destroy(kdlae_st_handle* h) { return train_destroy(h); }
 
-int kdlae_st_num_params(const kdlae_st_handle* h) { return h ? h->lay.size() : -1; }
+int kdlae_st_num_params(const kdlae_st_handle* h) { return train_num_params(h, -1); }
 
 int kdlae_st_param_info(const kdlae_st_handle* h, int i, const char** name, int64_t* numel, int64_t* offset) {
-  if (!h) return fail(KDLAE_EPARAM, "param index out of range");
-  return h->lay.info(i, name, numel, offset);
+  return train_param_info(h, i, name, numel, offset);
 }
 
-int64_t kdlae_st_num_floats(const kdlae_st_handle* h) { return h ? h->lay.total : -1; }
+int64_t kdlae_st_num_floats(const kdlae_st_handle* h) { return train_num_floats(h); }
 
 int64_t kdlae_st_workspace_bytes(const kdlae_st_handle* h, int B, int F, int H, int W) {
   if (!h) return -1;
@@ -494,8 +456,8 @@ int kdlae_st_forward(kdlae_st_handle* h, const float* theta, const float* x, int
   const int m = 1 << h->L;
   if (B <= 0 || F <= 0 || H <= 0 || W <= 0 || H % m || W % m)
     return fail(KDLAE_EINVAL_SHAPE, "KDLAE_student needs H and W divisible by 2^(len(hidden_channels)-1)");
-  Ctx c{h, theta, nullptr, reinterpret_cast<char*>(workspace), make_plan(h, B, F, H, W), (hipStream_t)stream,
-        B, F, H, W};
+  Ctx c{{&h->lay, theta, nullptr, reinterpret_cast<char*>(workspace)}, h, make_plan(h, B, F, H, W),
+        (hipStream_t)stream, B, F, H, W};
   if ((int64_t)c.pl.total > workspace_bytes) return fail(KDLAE_ESTATE, "training workspace too small");
   // the 32-bit limits that apply: the GEMMs' M / K (pixel counts) are int, and so is col2im's element
   // index (P * cin) for the convs whose input gradient goes through columns; im2col, the column
@@ -503,14 +465,9 @@ int kdlae_st_forward(kdlae_st_handle* h, const float* theta, const float* x, int
   if ((long long)B * F * H * W >= (1LL << 31) || c.pl.col2im_max >= (1LL << 31))
     return fail(KDLAE_EINVAL_SHAPE, "batch too large: B*F*H*W and P*cin of a column-gradient conv must be < 2^31");
   DeviceGuard dg(h->device);
-  h->valid = false;
+  h->last.valid = false;
   TRY(net_fwd(c, x, out));
-  h->valid = true;
-  h->B = B;
-  h->F = F;
-  h->H = H;
-  h->W = W;
-  h->ws = workspace;
+  h->last.set(workspace, B, F, H, W);
   h->x = x;
   return KDLAE_OK;
 }
@@ -518,38 +475,17 @@ int kdlae_st_forward(kdlae_st_handle* h, const float* theta, const float* x, int
 int kdlae_st_backward(kdlae_st_handle* h, const float* theta, const float* dout, float* grad, void* workspace,
                       int64_t workspace_bytes, void* stream) {
   if (!h || !theta || !dout || !grad || !workspace) return fail(KDLAE_ESTATE, "null argument");
-  if (!h->valid || h->ws != workspace)
-    return fail(KDLAE_ESTATE, "kdlae_st_backward needs a preceding kdlae_st_forward on the same workspace");
-  Ctx c{h, theta, grad, reinterpret_cast<char*>(workspace), make_plan(h, h->B, h->F, h->H, h->W),
-        (hipStream_t)stream, h->B, h->F, h->H, h->W};
+  TRY(h->last.check(workspace, "kdlae_st_backward", "kdlae_st_forward"));
+  const LastForward& f = h->last;
+  Ctx c{{&h->lay, theta, grad, reinterpret_cast<char*>(workspace)}, h, make_plan(h, f.B, f.F, f.H, f.W),
+        (hipStream_t)stream, f.B, f.F, f.H, f.W};
   if ((int64_t)c.pl.total > workspace_bytes) return fail(KDLAE_ESTATE, "training workspace too small");
   DeviceGuard dg(h->device);
   c.main_s = c.s;
-  if (!debug_flag("train_serial")) {
-    if (!h->side) {
-      HIPCHK(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
-      HIPCHK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-    }
-    c.side = h->side;
-  }
+  TRY(h->side.acquire(&c.side));
   HIPCHK(hipMemsetAsync(grad, 0, (size_t)h->lay.total * sizeof(float), c.s));  // the pad floats stay zero
   HIPCHK(hipMemsetAsync(c.buf(c.pl.zb), 0, 64 * sizeof(float), c.s));
   return net_bwd(c, h->x, dout);
-}
-
-int64_t kdlae_train_l1frames_scratch_floats(void) { return tr::l1frames_scratch_floats(); }
-
-int kdlae_train_l1frames(const float* pred, const float* target, int N, int frames, int64_t hw, float l1loss_weight,
-                         float temporal_weight, float binary, int reduction, float* dpred, float* loss, float* scratch,
-                         void* stream) {
-  if (!pred || !target || !dpred || !loss || !scratch) return fail(KDLAE_ESTATE, "null argument");
-  if (N <= 0 || frames <= 0 || hw <= 0) return fail(KDLAE_EINVAL_SHAPE, "empty loss input");
-  if (reduction != 0 && reduction != 1)
-    return fail(KDLAE_EINVAL_CONFIG, "reduction: 0 = 'mean', 1 = 'sum' ('max' / 'mix' are not implemented)");
-  HIPCHK(tr::launch_l1frames(pred, target, N, frames, hw, l1loss_weight, temporal_weight, binary, reduction, dpred,
-                             loss, scratch, (hipStream_t)stream));
-  return KDLAE_OK;
 }
 
 }  // extern "C"

@@ -23,6 +23,7 @@
 #include "../../include/kdlae.h"
 #include "param_layout.h"
 #include "runtime.h"
+#include "train_host.h"
 #include "train_kernels.h"
 
 using kdlae::al16;
@@ -45,11 +46,8 @@ struct BlockRec {
   float* wpo = nullptr;  // ffn.project_out weight with rows padded to ld4(hid) (odd hid only), zero pads
 };
 
-struct Saved {
-  int B = 0, H = 0, W = 0;
-  const void* ws = nullptr;
+struct Saved : kdlae::LastForward {
   size_t fwd_end = 0;
-  bool valid = false;
   float *img_h = nullptr, *pe = nullptr, *enc1 = nullptr, *dn1c = nullptr, *enc2 = nullptr, *dn2c = nullptr,
         *enc3 = nullptr, *dn3c = nullptr, *lat = nullptr, *cat3 = nullptr, *dec3 = nullptr, *cat2 = nullptr,
         *dec2 = nullptr, *cat1 = nullptr, *dec1 = nullptr, *ref = nullptr, *catp = nullptr, *ro = nullptr,
@@ -59,10 +57,11 @@ struct Saved {
 
 }  // namespace
 
-struct kdlae_tt_handle {
+// per gradient key offset: the (first, last) backward mark at which a pass writes it
+using TouchMap = std::map<int64_t, std::pair<int, int>>;
+
+struct kdlae_tt_handle : kdlae::TrainHandleBase {
   kdlae_t_config cfg{};
-  int device = 0;
-  kdlae::ParamLayout lay{4};  // state_dict order, every key 16-byte aligned
   Saved sv;
   int ws_B = -1, ws_H = -1, ws_W = -1;  // last kdlae_tt_workspace_bytes query (its dry run is cached)
   int64_t ws_bytes = -1;
@@ -76,28 +75,23 @@ struct kdlae_tt_handle {
   // cached, so a training step does not repeat the host-side dry run
   int mk_dsr = -1, mk_B = -1, mk_H = -1, mk_W = -1;
   size_t mk_fwd_end = 0, mk_peak = 0;
-  // per key offset the backward writes (dry run): the (first, last) mark at which it is written
-  std::map<int64_t, std::pair<int, int>> mk_touch;
+  // what the dry run of the backward writes
+  TouchMap mk_touch;
   // KDLAE_DEBUG=train_trace: per-launch event pairs of the current call, dumped to KDLAE_PROBE_DUMP
   struct TraceRec {
     std::string tag;
     hipEvent_t a, b;
   };
   std::vector<TraceRec> trace;
-  // backward side stream (non-blocking) and its fork / join events: the weight-gradient GEMMs and
-  // bias column sums run there, beside the input-gradient chain on the caller's stream
-  hipStream_t side = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  // the backward's side stream: the weight-gradient GEMMs and bias column sums run there
+  kdlae::SideStream side;
   // stage_bwd's lagged synchronisation: recorded after each block's last side launch (its scratch
   // region and gradient buffers are reused two blocks later)
   hipEvent_t ev_blk[2] = {nullptr, nullptr};
-  ~kdlae_tt_handle() {
+  ~kdlae_tt_handle() override {
     for (hipEvent_t e : mark_ev) (void)hipEventDestroy(e);
-    if (ev_fork) (void)hipEventDestroy(ev_fork);
-    if (ev_join) (void)hipEventDestroy(ev_join);
-    for (hipEvent_t e : {ev_blk[0], ev_blk[1]})
+    for (hipEvent_t e : ev_blk)
       if (e) (void)hipEventDestroy(e);
-    if (side) (void)hipStreamDestroy(side);
   }
 };
 
@@ -132,24 +126,23 @@ struct Ctx {
   char* base = nullptr;
   size_t off = 0, cap = 0, peak = 0;
   bool dry = true;
-  hipStream_t s = nullptr;  // the stream launches go to: main_s, or side_s inside a side segment
+  hipStream_t s = nullptr;  // the stream launches go to: main_s, or the side stream inside a side segment
   float* splitk = nullptr;   // split-K partials of the current stream (splitk_main / splitk_side)
   // backward side stream (kdlae_tt_backward*): a side segment (side_begin .. side_end) holds
   // launches that only READ buffers the main stream does not write until the next join.  Every
   // segment starts with a fork (the side stream waits for the main stream's current point), so side
   // work is ordered after all earlier main work, including reduction flushes; the main stream waits
   // for the side stream (join) at every flush, mark and block end, before a write to a buffer a
-  // pending side launch reads, and before scratch is released.  side_s == nullptr: one stream.
-  hipStream_t main_s = nullptr, side_s = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  hipEvent_t ev_blk[2] = {nullptr, nullptr};
+  // pending side launch reads, and before scratch is released.  side == nullptr: one stream.
+  hipStream_t main_s = nullptr;
+  kdlae::SideStream* side = nullptr;
   bool blk_rec[2] = {false, false};  // ev_blk[p] holds a record of this call (stage_bwd)
   float* splitk_main = nullptr;
   float* splitk_side = nullptr;
   bool in_side = false, side_pending = false;
   // gradient-ready marks (kdlae_tt_backward_marked): the dry run records, per key offset, the first
   // and last mark index at which its gradient was written; the real run records an event per mark
-  std::map<int64_t, std::pair<int, int>>* touch = nullptr;
+  TouchMap* touch = nullptr;
   int cur_mark = 0;
   bool record_marks = false;
   // launch trace (diagnostics only: KDLAE_DEBUG=train_trace); tag = the layer being sequenced
@@ -194,23 +187,17 @@ struct Ctx {
 int flush_reduce(Ctx& c);
 int flush_all(Ctx& c);
 
-int hip_fail(hipError_t e, const char* what) {
-  return fail(KDLAE_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
 // enter a side segment: the side stream waits for everything enqueued on the main stream so far
 int side_begin(Ctx& c) {
   if (c.in_side) return KDLAE_OK;
   c.splitk = c.splitk_side;
   c.in_side = true;
-  if (c.dry || !c.side_s) {
+  if (c.dry || !c.side) {
     c.splitk = c.splitk_main;  // one stream: the main stream's partials
     return KDLAE_OK;
   }
-  hipError_t e = hipEventRecord(c.ev_fork, c.main_s);
-  if (e == hipSuccess) e = hipStreamWaitEvent(c.side_s, c.ev_fork, 0);
-  if (e != hipSuccess) return hip_fail(e, "side stream fork");
-  c.s = c.side_s;
+  TRY(c.side->fork(c.main_s));
+  c.s = c.side->s;
   c.side_pending = true;
   return KDLAE_OK;
 }
@@ -226,23 +213,21 @@ int join(Ctx& c) {
   if (c.in_side) side_end(c);
   if (!c.side_pending) return KDLAE_OK;
   c.side_pending = false;
-  hipError_t e = hipEventRecord(c.ev_join, c.side_s);
-  if (e == hipSuccess) e = hipStreamWaitEvent(c.main_s, c.ev_join, 0);
-  return e == hipSuccess ? KDLAE_OK : hip_fail(e, "side stream join");
+  return c.side->join(c.main_s);
 }
 
 // record ev on the side stream after every side launch enqueued so far (no-op on one stream)
 int side_record(Ctx& c, hipEvent_t ev) {
-  if (c.dry || !c.side_s || !ev) return KDLAE_OK;
-  hipError_t e = hipEventRecord(ev, c.side_s);
-  return e == hipSuccess ? KDLAE_OK : hip_fail(e, "side stream event");
+  if (c.dry || !c.side || !ev) return KDLAE_OK;
+  HIPCHK(hipEventRecord(ev, c.side->s));
+  return KDLAE_OK;
 }
 
 // the main stream waits for a side-stream event recorded earlier (typically long complete)
 int main_wait(Ctx& c, hipEvent_t ev) {
-  if (c.dry || !c.side_s || !ev) return KDLAE_OK;
-  hipError_t e = hipStreamWaitEvent(c.main_s, ev, 0);
-  return e == hipSuccess ? KDLAE_OK : hip_fail(e, "side stream wait");
+  if (c.dry || !c.side || !ev) return KDLAE_OK;
+  HIPCHK(hipStreamWaitEvent(c.main_s, ev, 0));
+  return KDLAE_OK;
 }
 
 // a region of the reduction buffer for a queued reduction's partials (flushes when full)
@@ -329,8 +314,8 @@ int flush_all(Ctx& c) {
   Ctx::RedList& sl = c.rl[1];
   if (!sl.pend.empty()) {
     hipStream_t keep = c.s;
-    c.s = c.side_s && !c.dry ? c.side_s : c.main_s;
-    if (c.side_s && !c.dry) c.side_pending = true;
+    c.s = c.side && !c.dry ? c.side->s : c.main_s;
+    if (c.side && !c.dry) c.side_pending = true;
     LAUNCH(tr::launch_part_reduce_multi(sl.pend.data(), (int)sl.pend.size(), c.s));
     c.s = keep;
   }
@@ -518,8 +503,7 @@ int conv3_narrow(Ctx& c, const float* w, const float* bias, V in, int Cin, int C
 int pack_w3(Ctx& c, tr::TGemm& g, int N) {
   if (kdlae::debug_flag("train_w3_raw") || N % 4) return KDLAE_OK;
   float* wp = c.alloc((size_t)9 * g.Cg * N);
-  LAUNCH(tr::launch_pack_w3(g.B, g.Cg, N, g.bmode, wp, c.s));
-  tr::use_packed_w3(g, wp, N);
+  LAUNCH(tr::launch_pack_w3(g, N, wp, c.s));  // the dry run never launches g, so it needs no rewrite
   return KDLAE_OK;
 }
 
@@ -528,15 +512,10 @@ int conv3(Ctx& c, const std::string& n, V x, int Cin, int Cout, int Bn, int H, i
   int done = 0;
   TRY(conv3_narrow(c, c.W(n + ".weight"), c.W(n + ".bias"), x, Cin, Cout, Bn, H, W, dil, out, R, ldr, false, &done));
   if (done) return KDLAE_OK;
-  tr::TGemm g;
-  g.A = x.p; g.amode = 1; g.lda = x.ld; g.Cg = Cin;
-  g.B = c.W(n + ".weight"); g.bmode = 2;
+  tr::TGemm g = tr::conv3_fwd_gemm({x.p, x.ld, Cin}, c.W(n + ".weight"), c.W(n + ".bias"), {out.p, out.ld, Cout},
+                                   {Bn, H, W, dil});
   TRY(pack_w3(c, g, Cout));
-  g.C = out.p; g.scm = out.ld; g.scn = 1;
-  g.bias = c.W(n + ".bias");
   g.R = R; g.srm = ldr; g.srn = 1;
-  g.M = Bn * H * W; g.N = Cout; g.K = 9 * Cin;
-  g.Bn = Bn; g.H = H; g.W = W; g.dil = dil;
   // split-K when the pixel tiles alone leave the chip idle (the 16^2 / 32^2 Upsample convs: 72-144
   // tiles, K up to 3456); launch_tgemm only splits where that fills it
   g.partial = c.splitk;
@@ -558,13 +537,7 @@ int conv3_bwd(Ctx& c, const std::string& n, V x, V dy, int Cin, int Cout, int Bn
     LAUNCH(tr::launch_dw3_small(dy.p, dy.ld, x.p, x.ld, Cin, Cout, Bn, H, W, dil, part, nb, c.s));
     TRY(queue_reduce(c, part, nb, ncols, ncols, gw));
   } else {
-    tr::TGemm g;  // dW[co][ci][t] = sum_p dY[p,co] X[p + off_t, ci]
-    g.A = dy.p; g.sam = 1; g.sak = dy.ld;
-    g.B = x.p; g.bmode = 1; g.ldb = x.ld;
-    g.C = gw; g.scm = (long long)Cin * 9; g.scn = 9; g.bC2 = 1;
-    g.nz2 = 9;
-    g.M = Cout; g.N = Cin; g.K = (int)P;
-    g.Bn = Bn; g.H = H; g.W = W; g.dil = dil;
+    tr::TGemm g = tr::conv3_dw_gemm({dy.p, dy.ld, Cout}, {x.p, x.ld, Cin}, gw, {Bn, H, W, dil});
     g.partial = c.splitk;
     TRY(gemm(c, g, kSplitCap, n + " dW3"));
   }
@@ -575,14 +548,9 @@ int conv3_bwd(Ctx& c, const std::string& n, V x, V dy, int Cin, int Cout, int Bn
     int done = 0;
     TRY(conv3_narrow(c, c.W(n + ".weight"), nullptr, dy, Cout, Cin, Bn, H, W, dil, dx, R, ldr, true, &done));
     if (done) return KDLAE_OK;
-    tr::TGemm d;  // transposed conv: flipped taps, channels swapped
-    d.A = dy.p; d.amode = 1; d.lda = dy.ld; d.Cg = Cout;
-    d.B = c.W(n + ".weight"); d.bmode = 3;
+    tr::TGemm d = tr::conv3_dx_gemm({dy.p, dy.ld, Cout}, c.W(n + ".weight"), {dx.p, dx.ld, Cin}, {Bn, H, W, dil});
     TRY(pack_w3(c, d, Cin));
-    d.C = dx.p; d.scm = dx.ld; d.scn = 1;
     d.R = R; d.srm = ldr; d.srn = 1;
-    d.M = (int)P; d.N = Cin; d.K = 9 * Cout;
-    d.Bn = Bn; d.H = H; d.W = W; d.dil = dil;
     d.partial = c.splitk;
     TRY(gemm(c, d, kSplitCap, n + " dX3"));
   }
@@ -821,7 +789,7 @@ int stage_fwd(Ctx& c, const std::string& name, int n, int C, int heads, int Bn, 
 // gradient-ready marks need them); the stage ends with one either way, the result copied into d.
 int stage_bwd(Ctx& c, const std::string& name, float* d) {
   const auto& recs = c.h->sv.stages.at(name);
-  const bool lag = !c.record_marks && !c.dry && c.side_s && KDLAE_TRAIN_LAG;
+  const bool lag = !c.record_marks && !c.dry && c.side && KDLAE_TRAIN_LAG;
   const BlockRec& r0 = recs.front();
   const size_t dn = (size_t)r0.Bn * r0.H * r0.W * r0.C;
   const size_t off0 = c.off;
@@ -832,12 +800,12 @@ int stage_bwd(Ctx& c, const std::string& name, float* d) {
   for (int i = (int)recs.size() - 1, k = 0; i >= 0; --i, ++k) {
     const int par = k & 1;
     c.off = par ? e0 : base;  // the same layout with or without lag, so the dry run sizes it
-    if (lag && c.blk_rec[par]) TRY(main_wait(c, c.ev_blk[par]));
+    if (lag && c.blk_rec[par]) TRY(main_wait(c, c.h->ev_blk[par]));
     size_t ext = 0;
     TRY(block_bwd(c, recs[i], dbuf[k % 3], dbuf[(k + 1) % 3], lag, &ext));
     if (par == 0) e0 = ext;
     if (lag) {
-      TRY(side_record(c, c.ev_blk[par]));
+      TRY(side_record(c, c.h->ev_blk[par]));
       c.blk_rec[par] = true;
       ++c.cur_mark;  // mark() without its flush and join
     } else {
@@ -1077,23 +1045,12 @@ void ctx_init(Ctx& c, const kdlae_tt_handle* h, void* ws, size_t ws_bytes, bool 
   c.rl[1].red = c.alloc(c.red_cap);
 }
 
-// the backward's side stream (created once per handle, on its device); KDLAE_DEBUG=train_serial
-// keeps every launch on the caller's stream (A/B and diagnostics: same results either way)
+// the backward's side stream and stage_bwd's two block events, created once per handle on its device
+// (KDLAE_DEBUG=train_serial: neither; every launch on the caller's stream, same results)
 int use_side_stream(Ctx& c, kdlae_tt_handle* h) {
-  if (kdlae::debug_flag("train_serial")) return KDLAE_OK;
-  if (!h->side) {
-    hipError_t e = hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming);
-    for (hipEvent_t* ev : {&h->ev_blk[0], &h->ev_blk[1]})
-      if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
-    if (e != hipSuccess) return hip_fail(e, "backward side stream");
-  }
-  c.side_s = h->side;
-  c.ev_fork = h->ev_fork;
-  c.ev_join = h->ev_join;
-  c.ev_blk[0] = h->ev_blk[0];
-  c.ev_blk[1] = h->ev_blk[1];
+  TRY(h->side.acquire(&c.side));
+  for (hipEvent_t& ev : h->ev_blk)
+    if (c.side && !ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
   return KDLAE_OK;
 }
 
@@ -1115,10 +1072,50 @@ void trace_dump(kdlae_tt_handle* h, hipStream_t s, const char* phase) {
   h->trace.clear();
 }
 
+// The backward's dry run from the end of the last forward: its workspace peak, and (marked backward)
+// the mark count and, per gradient key offset, the first and last mark at which it is written.
+int bwd_dry(const kdlae_tt_handle* h, const float* dhq, const float* dsr, bool has_dsr, float* grad, TouchMap* touch,
+            size_t* peak, int* nmarks) {
+  Ctx d;
+  ctx_init(d, h, nullptr, 0, true, nullptr, h->sv.B, h->sv.H, h->sv.W);
+  d.off = h->sv.fwd_end;
+  d.gr = grad;
+  d.touch = touch;
+  TRY(net_bwd(d, dhq, dsr, has_dsr));
+  *peak = d.peak;
+  if (nmarks) *nmarks = d.cur_mark;
+  return KDLAE_OK;
+}
+
+// The backward's launches.  written != null: the marked backward (an event per planned mark, a full
+// flush + join per block, the keys it writes recorded into *written).
+int bwd_run(kdlae_tt_handle* h, const float* theta, const float* dhq, const float* dsr, bool has_dsr, float* grad,
+            void* ws, size_t ws_bytes, hipStream_t stream, TouchMap* written) {
+  kdlae::DeviceGuard dg(h->device);
+  Ctx c;
+  ctx_init(c, h, ws, ws_bytes, false, stream, h->sv.B, h->sv.H, h->sv.W);
+  c.th = theta;
+  c.gr = grad;
+  c.off = h->sv.fwd_end;
+  c.record_marks = written != nullptr;
+  c.touch = written;
+  if (kdlae::debug_flag("train_trace")) c.trace = &h->trace;
+  int rc = use_side_stream(c, h);
+  if (rc) return rc;
+  hipError_t e = hipMemsetAsync(grad, 0, (size_t)h->lay.total * sizeof(float), stream);
+  if (e != hipSuccess) return fail(KDLAE_EHIP, hipGetErrorString(e));
+  rc = net_bwd(c, dhq, dsr, has_dsr);
+  if (rc == KDLAE_OK) rc = flush_all(c);
+  if (rc != KDLAE_OK) (void)join(c);  // leave no side launch unjoined, even on an error path
+  trace_dump(h, c.s, "bwd");
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
 
+// kdlae_tt_* report a null argument as KDLAE_EINVAL_CONFIG (kdlae_st_* and asdqe_train_*: KDLAE_ESTATE)
 int kdlae_tt_create(const kdlae_t_config* cfg, int device, kdlae_tt_handle** out) {
   if (!cfg || !out) return fail(KDLAE_EINVAL_CONFIG, "null argument");
   int rc = validate(*cfg);
@@ -1131,19 +1128,16 @@ int kdlae_tt_create(const kdlae_t_config* cfg, int device, kdlae_tt_handle** out
   return KDLAE_OK;
 }
 
-int kdlae_tt_destroy(kdlae_tt_handle* h) {
-  delete h;
-  return KDLAE_OK;
-}
+int kdlae_tt_destroy(kdlae_tt_handle* h) { return kdlae::train_destroy(h); }
 
-int kdlae_tt_num_params(const kdlae_tt_handle* h) { return h ? h->lay.size() : 0; }
+// a null handle has 0 parameters here (-1 in kdlae_st_* and asdqe_train_*)
+int kdlae_tt_num_params(const kdlae_tt_handle* h) { return kdlae::train_num_params(h, 0); }
 
 int kdlae_tt_param_info(const kdlae_tt_handle* h, int index, const char** name, int64_t* numel, int64_t* offset) {
-  if (!h) return fail(KDLAE_EPARAM, "param index out of range");
-  return h->lay.info(index, name, numel, offset);
+  return kdlae::train_param_info(h, index, name, numel, offset);
 }
 
-int64_t kdlae_tt_num_floats(const kdlae_tt_handle* h) { return h ? h->lay.total : -1; }
+int64_t kdlae_tt_num_floats(const kdlae_tt_handle* h) { return kdlae::train_num_floats(h); }
 
 static int check_shape(int B, int H, int W) {
   if (B <= 0 || H <= 0 || W <= 0) return fail(KDLAE_EINVAL_SHAPE, "B, H, W must be positive");
@@ -1193,66 +1187,36 @@ int kdlae_tt_forward(kdlae_tt_handle* h, const float* theta, const float* img, c
   rc = net_fwd(c, img, rate, hq, sr);
   trace_dump(h, c.s, "fwd");
   if (rc) return rc;
-  h->sv.ws = ws;
+  h->sv.set(ws, B, 1, H, W);
   h->sv.fwd_end = c.off;
-  h->sv.valid = true;
   return KDLAE_OK;
 }
 
 int kdlae_tt_backward(kdlae_tt_handle* h, const float* theta, const float* dhq, const float* dsr, float* grad, void* ws,
                       size_t ws_bytes, void* stream) {
   if (!h || !theta || !grad || !ws) return fail(KDLAE_EINVAL_CONFIG, "null argument");
-  if (!h->sv.valid || h->sv.ws != ws)
-    return fail(KDLAE_ESTATE, "kdlae_tt_backward needs a preceding kdlae_tt_forward on the same workspace");
+  TRY(h->sv.check(ws, "kdlae_tt_backward", "kdlae_tt_forward"));
   const bool has_dsr = h->cfg.static_train && dsr;
-  {  // size the backward before launching anything
-    Ctx d;
-    ctx_init(d, h, nullptr, 0, true, nullptr, h->sv.B, h->sv.H, h->sv.W);
-    d.off = h->sv.fwd_end;
-    int rc = net_bwd(d, dhq, dsr, has_dsr);
-    if (rc) return rc;
-    if (d.peak > ws_bytes) return fail(KDLAE_ESTATE, "training workspace too small for the backward");
-  }
-  kdlae::DeviceGuard dg(h->device);
-  Ctx c;
-  ctx_init(c, h, ws, ws_bytes, false, (hipStream_t)stream, h->sv.B, h->sv.H, h->sv.W);
-  c.th = theta;
-  c.gr = grad;
-  c.off = h->sv.fwd_end;
-  if (kdlae::debug_flag("train_trace")) c.trace = &h->trace;
-  int rc = use_side_stream(c, h);
-  if (rc) return rc;
-  hipError_t e = hipMemsetAsync(grad, 0, (size_t)h->lay.total * sizeof(float), (hipStream_t)stream);
-  if (e != hipSuccess) return fail(KDLAE_EHIP, hipGetErrorString(e));
-  rc = net_bwd(c, dhq, dsr, has_dsr);
-  if (rc == KDLAE_OK) rc = flush_all(c);
-  if (rc != KDLAE_OK) (void)join(c);  // leave no side launch unjoined, even on an error path
-  trace_dump(h, c.s, "bwd");
-  return rc;
+  size_t peak = 0;  // size the backward before launching anything
+  TRY(bwd_dry(h, dhq, dsr, has_dsr, grad, nullptr, &peak, nullptr));
+  if (peak > ws_bytes) return fail(KDLAE_ESTATE, "training workspace too small for the backward");
+  return bwd_run(h, theta, dhq, dsr, has_dsr, grad, ws, ws_bytes, (hipStream_t)stream, nullptr);
 }
 
+// the backward above plus: the mark plan (cached per shape), the event pool, and the check that the
+// launches wrote the keys the plan was made from
 int kdlae_tt_backward_marked(kdlae_tt_handle* h, const float* theta, const float* dhq, const float* dsr, float* grad,
                              void* ws, size_t ws_bytes, void* stream) {
   if (!h || !theta || !grad || !ws) return fail(KDLAE_EINVAL_CONFIG, "null argument");
-  if (!h->sv.valid || h->sv.ws != ws)
-    return fail(KDLAE_ESTATE, "kdlae_tt_backward_marked needs a preceding kdlae_tt_forward on the same workspace");
+  TRY(h->sv.check(ws, "kdlae_tt_backward_marked", "kdlae_tt_forward"));
   const bool has_dsr = h->cfg.static_train && dsr;
   const bool cached = h->mk_dsr == (int)has_dsr && h->mk_B == h->sv.B && h->mk_H == h->sv.H && h->mk_W == h->sv.W &&
                       h->mk_fwd_end == h->sv.fwd_end;
   if (!cached) {
-    std::map<int64_t, std::pair<int, int>> touch;
+    // size the backward and find, per mark, which suffix of the flat buffer is final there
+    TouchMap touch;
     int nmarks = 0;
-    {  // size the backward and find, per mark, which suffix of the flat buffer is final there
-      Ctx d;
-      ctx_init(d, h, nullptr, 0, true, nullptr, h->sv.B, h->sv.H, h->sv.W);
-      d.off = h->sv.fwd_end;
-      d.gr = grad;
-      d.touch = &touch;
-      int rc = net_bwd(d, dhq, dsr, has_dsr);
-      if (rc) return rc;
-      nmarks = d.cur_mark;
-      h->mk_peak = d.peak;
-    }
+    TRY(bwd_dry(h, dhq, dsr, has_dsr, grad, &touch, &h->mk_peak, &nmarks));
     // mark m closes the suffix [lo, total) when lo = the lowest offset written by mark m and every
     // key at or above lo is untouched (its gradient is the zero fill) or last written by mark m.
     // One pass from the end of the flat buffer: closed[m] <=> max over keys >= lo of last-write <= m
@@ -1289,24 +1253,8 @@ int kdlae_tt_backward_marked(kdlae_tt_handle* h, const float* theta, const float
     if (er != hipSuccess) return fail(KDLAE_EHIP, hipGetErrorString(er));
     h->mark_ev.push_back(e);
   }
-  Ctx c;
-  ctx_init(c, h, ws, ws_bytes, false, (hipStream_t)stream, h->sv.B, h->sv.H, h->sv.W);
-  c.th = theta;
-  c.gr = grad;
-  c.off = h->sv.fwd_end;
-  c.record_marks = true;
-  std::map<int64_t, std::pair<int, int>> written;  // what the real run writes, checked against the marks
-  c.touch = &written;
-  if (kdlae::debug_flag("train_trace")) c.trace = &h->trace;
-  int rc = use_side_stream(c, h);
-  if (rc) return rc;
-  hipError_t e = hipMemsetAsync(grad, 0, (size_t)h->lay.total * sizeof(float), (hipStream_t)stream);
-  if (e != hipSuccess) return fail(KDLAE_EHIP, hipGetErrorString(e));
-  rc = net_bwd(c, dhq, dsr, has_dsr);
-  if (rc == KDLAE_OK) rc = flush_all(c);
-  if (rc != KDLAE_OK) (void)join(c);
-  trace_dump(h, c.s, "bwd");
-  if (rc) return rc;
+  TouchMap written;  // what the real run writes, checked against the marks
+  TRY(bwd_run(h, theta, dhq, dsr, has_dsr, grad, ws, ws_bytes, (hipStream_t)stream, &written));
   // every gradient the launches wrote must have been written by the dry run the marks came from, at
   // the same (first, last) marks: a write it missed, or one moved past the mark that declares its key
   // final, could be all-reduced before it lands
@@ -1345,72 +1293,6 @@ int kdlae_tt_mark_sync(kdlae_tt_handle* h, int j) {
   kdlae::DeviceGuard dg(h->device);
   hipError_t e = hipEventSynchronize(h->mark_ev[j]);
   return e == hipSuccess ? KDLAE_OK : fail(KDLAE_EHIP, hipGetErrorString(e));
-}
-
-int64_t kdlae_train_l1sr_scratch_floats(void) { return 4 * 1024; }
-
-int kdlae_train_l1sr(const float* pred_hq, const float* gt_hq, int64_t n_hq, const float* pred_sr, const float* gt_sr,
-                     int64_t n_sr, float* dhq, float* dsr, float* loss, float* scratch, void* stream) {
-  if (!pred_hq || !gt_hq || !loss || !scratch || n_hq <= 0) return fail(KDLAE_EINVAL_CONFIG, "null argument");
-  if (pred_sr && (!gt_sr || n_sr <= 0)) return fail(KDLAE_EINVAL_CONFIG, "pred_sr without gt_sr / n_sr");
-  hipStream_t s = (hipStream_t)stream;
-  const int nb = 1024;
-  float* p0 = scratch;
-  float* p1 = scratch + 2 * nb;
-  // L1LossSr (losses.py:159-170): 0.5 l1(hq) + 0.25 l1(sr) + 0.25 (shadow(hq) + shadow(sr))
-  hipError_t e = tr::launch_l1sr(pred_hq, gt_hq, n_hq, 0.5f, dhq, p0, nb, s);
-  if (e == hipSuccess && pred_sr) e = tr::launch_l1sr(pred_sr, gt_sr, n_sr, 0.25f, dsr, p1, nb, s);
-  if (e == hipSuccess)
-    e = tr::launch_l1sr_final(p0, nb, n_hq, 0.5f, 0.25f, pred_sr ? p1 : nullptr, pred_sr ? nb : 0, pred_sr ? n_sr : 1,
-                              0.25f, 0.25f, loss, s);
-  if (e != hipSuccess) return fail(KDLAE_EHIP, hipGetErrorString(e));
-  return KDLAE_OK;
-}
-
-int64_t kdlae_train_adamw_scratch_floats(void) { return 2048 + 2; }
-
-int kdlae_train_clip_adamw(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float gscale,
-                           float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-                           const int64_t* ranges, int nranges, float* scratch, void* stream) {
-  if (!theta || !grad || !exp_avg || !exp_avg_sq || !scratch || n <= 0 || step < 1 || nranges < 0 ||
-      (nranges > 0 && !ranges))
-    return fail(KDLAE_EINVAL_CONFIG, "bad argument");
-  for (int r = 0; r < nranges; ++r)
-    if (ranges[2 * r] < 0 || ranges[2 * r] > ranges[2 * r + 1] || ranges[2 * r + 1] > n)
-      return fail(KDLAE_EINVAL_CONFIG, "bad parameter range");
-  hipStream_t s = (hipStream_t)stream;
-  const int nb = 2048;
-  float* state = scratch + nb;  // [0] = grad norm, [1] = applied grad scale
-  // the norm covers every gradient (clip_grad_norm_ over net_g.parameters()); the update only the
-  // parameters that received a gradient (torch.optim skips p.grad is None, e.g. output_param when
-  // params != 'cat')
-  hipError_t e = tr::launch_sumsq(grad, n, scratch, nb, s);
-  if (e == hipSuccess) e = tr::launch_clip_coef(scratch, nb, gscale, max_norm, state, s);
-  const int64_t whole[2] = {0, n};
-  const int64_t* rg = nranges ? ranges : whole;
-  for (int r = 0; r < (nranges ? nranges : 1) && e == hipSuccess; ++r) {
-    const int64_t b = rg[2 * r], len = rg[2 * r + 1] - b;
-    if (len > 0)
-      e = tr::launch_adamw(theta + b, grad + b, exp_avg + b, exp_avg_sq + b, len, state, lr, beta1, beta2, eps,
-                           weight_decay, step, s);
-  }
-  if (e != hipSuccess) return fail(KDLAE_EHIP, hipGetErrorString(e));
-  return KDLAE_OK;
-}
-
-int kdlae_train_mixup(const float* in, float* out, int B, int64_t per_sample, const int* perm, float lam,
-                      void* stream) {
-  if (!in || !out || !perm || B <= 0 || per_sample <= 0 || in == out) return fail(KDLAE_EINVAL_CONFIG, "bad argument");
-  hipError_t e = tr::launch_mixup(in, out, B, per_sample, perm, lam, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(KDLAE_EHIP, hipGetErrorString(e));
-  return KDLAE_OK;
-}
-
-int kdlae_train_ema(float* ema, const float* theta, int64_t n, float decay, void* stream) {
-  if (!ema || !theta || n <= 0) return fail(KDLAE_EINVAL_CONFIG, "bad argument");
-  hipError_t e = tr::launch_ema(ema, theta, n, decay, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(KDLAE_EHIP, hipGetErrorString(e));
-  return KDLAE_OK;
 }
 
 }  // extern "C"

@@ -145,6 +145,59 @@ inline void use_packed_w3(TGemm& g, float* wp, int N) {
   g.sbk = N;
   g.sbn = 1;
 }
+// ... both at once: the pack launch into wp (9 Cg N floats) and the rewrite.  The hosts differ only in
+// where wp lives (KDLAE-T: a workspace allocation per conv; ASDQE: one fixed buffer).
+inline hipError_t launch_pack_w3(TGemm& g, int N, float* wp, hipStream_t s) {
+  const hipError_t e = launch_pack_w3(g.B, g.Cg, N, g.bmode, wp, s);
+  use_packed_w3(g, wp, N);
+  return e;
+}
+
+// The three GEMMs of a 3x3 conv (zero padding dil) between NHWC views x [Bn,H,W,x.C] and y
+// [Bn,H,W,y.C] with an OIHW weight w [y.C][x.C][3][3].  Each returns the descriptor with everything
+// set but `partial` and the packed-weight substitution (launch_pack_w3); a residual is the caller's.
+struct Nhwc {
+  float* p;
+  long long ld;
+  int C;
+};
+struct ConvGeo {
+  int Bn, H, W, dil;
+  int pixels() const { return Bn * H * W; }
+  void put(TGemm& g) const { g.Bn = Bn; g.H = H; g.W = W; g.dil = dil; }
+};
+// y = conv(x, w) + bias
+inline TGemm conv3_fwd_gemm(Nhwc x, const float* w, const float* bias, Nhwc y, const ConvGeo& o) {
+  TGemm g;
+  g.A = x.p; g.amode = 1; g.lda = x.ld; g.Cg = x.C;
+  g.B = w; g.bmode = 2;
+  g.C = y.p; g.scm = y.ld; g.scn = 1;
+  g.bias = bias;
+  g.M = o.pixels(); g.N = y.C; g.K = 9 * x.C;
+  o.put(g);
+  return g;
+}
+// gw[co][ci][t] = sum_p dy[p, co] x[p + off_t, ci]
+inline TGemm conv3_dw_gemm(Nhwc dy, Nhwc x, float* gw, const ConvGeo& o) {
+  TGemm g;
+  g.A = dy.p; g.sam = 1; g.sak = dy.ld;
+  g.B = x.p; g.bmode = 1; g.ldb = x.ld;
+  g.C = gw; g.scm = (long long)x.C * 9; g.scn = 9; g.bC2 = 1;
+  g.nz2 = 9;
+  g.M = dy.C; g.N = x.C; g.K = o.pixels();
+  o.put(g);
+  return g;
+}
+// dx = the transposed conv of dy: flipped taps, channels swapped
+inline TGemm conv3_dx_gemm(Nhwc dy, const float* w, Nhwc dx, const ConvGeo& o) {
+  TGemm g;
+  g.A = dy.p; g.amode = 1; g.lda = dy.ld; g.Cg = dy.C;
+  g.B = w; g.bmode = 3;
+  g.C = dx.p; g.scm = dx.ld; g.scn = 1;
+  g.M = o.pixels(); g.N = dx.C; g.K = 9 * dy.C;
+  o.put(g);
+  return g;
+}
 // out[p, 0:C] (= or +=) in[p, 0:C]; zero_to > C also zeroes out[p, C:zero_to] (a padded copy)
 hipError_t launch_copy_cols(const float* in, int ldi, float* out, int ldo, int C, long long P, int accumulate,
                             hipStream_t s, int zero_to = 0);

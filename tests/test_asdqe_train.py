@@ -112,3 +112,62 @@ def test_bad_config_is_refused():
     cfg.in_channels, cfg.dim = 3, 24
     h = ctypes.c_void_p()
     assert L.asdqe_train_create(ctypes.byref(cfg), 0, ctypes.byref(h)) == 2
+
+
+def test_null_handle_and_null_argument_returns():
+    """What every asdqe_train_* entry answers without a device: return value, KDLAE_E* code, error text."""
+    from tests.util import FAKE, failed, silent
+    L, h = _handle(dict())
+    try:
+        cfg = _lib.AConfig()
+        cfg.in_channels, cfg.dim = 3, 16
+        failed(L.asdqe_train_create(None, 0, ctypes.byref(h)), 6, "null argument")
+        failed(L.asdqe_train_create(ctypes.byref(cfg), 0, None), 6, "null argument")
+        silent(lambda: L.asdqe_train_destroy(None), 0)
+        silent(lambda: L.asdqe_train_num_params(None), -1)
+        silent(lambda: L.asdqe_train_num_floats(None), -1)
+        silent(lambda: L.asdqe_train_num_stat_floats(None), -1)
+        silent(lambda: L.asdqe_train_workspace_bytes(None, 2, 40, 56), -1)
+        failed(L.asdqe_train_param_info(None, 0, None, None, None), 4, "param index out of range")
+        failed(L.asdqe_train_param_info(h, L.asdqe_train_num_params(h), None, None, None), 4,
+               "param index out of range")
+        big = 1 << 40
+        fwd = lambda a, B=2, ws_bytes=0: L.asdqe_train_forward(h, a[0], a[1], a[2], a[3], B, 40, 56, None, None,
+                                                               a[4], a[5], ws_bytes, None)
+        failed(L.asdqe_train_forward(None, FAKE, FAKE, FAKE, FAKE, 2, 40, 56, None, None, FAKE, FAKE, 0, None), 6,
+               "null argument")
+        failed(L.asdqe_train_backward(None, FAKE, FAKE, FAKE, 0, FAKE, 0, None), 6, "null argument")
+        for miss in range(6):  # theta, stats, lq, gt, score, workspace
+            a = [FAKE] * 6
+            a[miss] = None
+            failed(fwd(a), 6, "null argument")
+        for miss in range(4):  # theta, dscore, grad, workspace
+            a = [FAKE] * 4
+            a[miss] = None
+            failed(L.asdqe_train_backward(h, a[0], a[1], a[2], 0, a[3], 0, None), 6, "null argument")
+        failed(fwd([FAKE] * 6, B=0), 1, "B, H, W must be positive")
+        failed(L.asdqe_train_workspace_bytes(h, 0, 40, 56), -1, "B, H, W must be positive")
+        failed(fwd([FAKE] * 6), 6, "training workspace too small")
+        for miss in (0, 1, 5):
+            a = [FAKE] * 6
+            a[miss] = FAKE + 8
+            failed(fwd(a, ws_bytes=big), 6, "theta, stats and the workspace must be 16-byte aligned")
+        failed(L.asdqe_train_backward(h, FAKE, FAKE, FAKE, 0, FAKE, big, None), 6,
+               "asdqe_train_backward needs a preceding asdqe_train_forward on the same workspace")
+    finally:
+        L.asdqe_train_destroy(h)
+    cfg.dim = 24
+    failed(L.asdqe_train_create(ctypes.byref(cfg), 0, ctypes.byref(h)), 2,
+           "dim must be a multiple of 16 in 16..256 on the HIP path")
+    assert h.value is None
+
+
+# asdqe_train_workspace_bytes of commit e977bd4 (make_plan is host code) at 2 x 40 x 56: the default
+# dim (16) and dim 32
+@pytest.mark.parametrize("dim,want", [(16, 102514688), (32, 126239488)])
+def test_workspace_bytes_pinned(dim, want):
+    L, h = _handle(dict(dim=dim))
+    try:
+        assert L.asdqe_train_workspace_bytes(h, 2, 40, 56) == want
+    finally:
+        L.asdqe_train_destroy(h)

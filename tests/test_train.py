@@ -252,3 +252,79 @@ def test_lr_schedule_matches_reference_scheduler():
     # linear warm-up (base_model.py:194-205) when warmup_iter > current_iter
     fake2 = types.SimpleNamespace(scheduler=None, init_lr=1e-4, lr=1e-4)
     assert abs(KDLAETrainer.update_learning_rate(fake2, 5, warmup_iter=10) - 5e-5) < 1e-15
+
+
+TINY = dict(dim=16, num_blocks=[1, 1, 1, 1], num_refinement_blocks=1)
+
+
+def test_null_handle_and_null_argument_returns():
+    """What every kdlae_tt_* entry answers without a device: return value, KDLAE_E* code, error text."""
+    from tests.util import FAKE, failed, silent
+    L = _lib.lib()
+    h = ctypes.c_void_p()
+    cfg = KDLAE_teacher(**TINY)._c_config()
+    failed(L.kdlae_tt_create(None, 0, ctypes.byref(h)), 2, "null argument")
+    failed(L.kdlae_tt_create(ctypes.byref(cfg), 0, None), 2, "null argument")
+    silent(lambda: L.kdlae_tt_destroy(None), 0)
+    silent(lambda: L.kdlae_tt_num_params(None), 0)  # the other two training handles answer -1
+    silent(lambda: L.kdlae_tt_num_floats(None), -1)
+    silent(lambda: L.kdlae_tt_workspace_bytes(None, 1, 32, 32), -1)
+    silent(lambda: L.kdlae_tt_mark_count(None), -1)
+    silent(lambda: L.kdlae_tt_mark_lo(None, 0), -1)
+    failed(L.kdlae_tt_param_info(None, 0, None, None, None), 4, "param index out of range")
+    failed(L.kdlae_tt_mark_wait(None, 0, None), 4, "mark index out of range")
+    failed(L.kdlae_tt_mark_sync(None, 0), 4, "mark index out of range")
+    failed(L.kdlae_tt_forward(None, FAKE, FAKE, FAKE, 1, 32, 32, FAKE, FAKE, FAKE, 0, None), 2, "null argument")
+    failed(L.kdlae_tt_backward(None, FAKE, FAKE, FAKE, FAKE, FAKE, 0, None), 2, "null argument")
+    failed(L.kdlae_tt_backward_marked(None, FAKE, FAKE, FAKE, FAKE, FAKE, 0, None), 2, "null argument")
+    _, h = _tt_handle(KDLAE_teacher(**TINY))
+    try:
+        failed(L.kdlae_tt_param_info(h, -1, None, None, None), 4, "param index out of range")
+        failed(L.kdlae_tt_param_info(h, L.kdlae_tt_num_params(h), None, None, None), 4, "param index out of range")
+        silent(lambda: L.kdlae_tt_mark_count(h), 0)
+        silent(lambda: L.kdlae_tt_mark_lo(h, 0), -1)
+        failed(L.kdlae_tt_mark_sync(h, 0), 4, "mark index out of range")
+        for miss in range(4):  # theta, img, hq, ws
+            a = [FAKE] * 4
+            a[miss] = None
+            failed(L.kdlae_tt_forward(h, a[0], a[1], FAKE, 1, 32, 32, a[2], FAKE, a[3], 0, None), 2, "null argument")
+        fwd = lambda B, H, W, rate=FAKE, sr=FAKE: L.kdlae_tt_forward(h, FAKE, FAKE, rate, B, H, W, FAKE, sr, FAKE, 0, None)
+        failed(fwd(0, 32, 32), 1, "B, H, W must be positive")
+        failed(fwd(1, 36, 40), 1, "H and W must be divisible by 8 (pixel_unshuffle x3, KDLAE_model.py:186-187)")
+        failed(fwd(1 << 20, 32, 32), 1, "too many pixels for one step")
+        failed(fwd(1, 32, 32, rate=None), 2, "params='cat' needs denoise_rate")
+        failed(fwd(1, 32, 32, sr=None), 2, "static='train' needs the sr output")
+        failed(fwd(1, 32, 32), 6, "training workspace too small")
+        failed(L.kdlae_tt_workspace_bytes(h, 1, 36, 40), -1,
+               "H and W must be divisible by 8 (pixel_unshuffle x3, KDLAE_model.py:186-187)")
+        for name in ("kdlae_tt_backward", "kdlae_tt_backward_marked"):
+            bwd = getattr(L, name)
+            for miss in range(3):  # theta, grad, ws
+                a = [FAKE] * 3
+                a[miss] = None
+                failed(bwd(h, a[0], FAKE, FAKE, a[1], a[2], 0, None), 2, "null argument")
+            failed(bwd(h, FAKE, None, None, FAKE, FAKE, 0, None), 6,
+                   name + " needs a preceding kdlae_tt_forward on the same workspace")
+    finally:
+        L.kdlae_tt_destroy(h)
+    bad = KDLAE_teacher(**TINY)._c_config()
+    bad.dim = 15
+    failed(L.kdlae_tt_create(ctypes.byref(bad), 0, ctypes.byref(h)), 2,
+           "training path: dim must be even and 8*dim <= 512 (LayerNorm wave kernel)")
+
+
+# kdlae_tt_workspace_bytes of commit e977bd4 (the dry run is host code): the bench config at the
+# KDLAET.yml patch setting, and the tiny config with and without the super-resolution branch
+@pytest.mark.parametrize("kw,shape,want", [
+    (None, (6, 128, 128), 22962137088),
+    (dict(TINY, static="train"), (1, 32, 32), 159098624),
+    (dict(TINY, static="no"), (1, 32, 32), 151396096),
+])
+def test_workspace_bytes_pinned(kw, shape, want):
+    from bench import KW
+    L, h = _tt_handle(KDLAE_teacher(**(kw or KW)))
+    try:
+        assert L.kdlae_tt_workspace_bytes(h, *shape) == want
+        assert L.kdlae_tt_workspace_bytes(h, *shape) == want  # the cached answer
+    finally:
+        L.kdlae_tt_destroy(h)

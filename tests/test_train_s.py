@@ -118,3 +118,69 @@ def test_training_handle_layout():
         assert L.kdlae_st_workspace_bytes(h, 2, 7, 30, 32) == -1  # H % 4 != 0
     finally:
         L.kdlae_st_destroy(h)
+
+
+def _st_handle(hc=(16, 32, 64)):
+    L = _lib.lib()
+    cfg = _lib.SConfig()
+    cfg.inp_channels = cfg.out_channels = 1
+    cfg.residual = 1
+    cfg.num_hidden = len(hc)
+    for i, v in enumerate(hc):
+        cfg.hidden_channels[i] = v
+    cfg.kernel_size = 3
+    h = ctypes.c_void_p()
+    return L, cfg, h, L.kdlae_st_create(ctypes.byref(cfg), 0, ctypes.byref(h))
+
+
+def test_null_handle_and_null_argument_returns():
+    """What every kdlae_st_* entry answers without a device: return value, KDLAE_E* code, error text."""
+    from tests.util import FAKE, failed, silent
+    L, cfg, h, rc = _st_handle()
+    assert rc == 0
+    try:
+        failed(L.kdlae_st_create(None, 0, ctypes.byref(h)), 6, "null argument")
+        failed(L.kdlae_st_create(ctypes.byref(cfg), 0, None), 6, "null argument")
+        silent(lambda: L.kdlae_st_destroy(None), 0)
+        silent(lambda: L.kdlae_st_num_params(None), -1)
+        silent(lambda: L.kdlae_st_num_floats(None), -1)
+        silent(lambda: L.kdlae_st_workspace_bytes(None, 1, 1, 32, 32), -1)
+        failed(L.kdlae_st_param_info(None, 0, None, None, None), 4, "param index out of range")
+        failed(L.kdlae_st_param_info(h, L.kdlae_st_num_params(h), None, None, None), 4, "param index out of range")
+        failed(L.kdlae_st_forward(None, FAKE, FAKE, 1, 1, 32, 32, FAKE, FAKE, 0, None), 6, "null argument")
+        failed(L.kdlae_st_backward(None, FAKE, FAKE, FAKE, FAKE, 0, None), 6, "null argument")
+        for miss in range(4):  # theta, x, out, workspace
+            a = [FAKE] * 4
+            a[miss] = None
+            failed(L.kdlae_st_forward(h, a[0], a[1], 1, 1, 32, 32, a[2], a[3], 0, None), 6, "null argument")
+        for miss in range(4):  # theta, dout, grad, workspace
+            a = [FAKE] * 4
+            a[miss] = None
+            failed(L.kdlae_st_backward(h, a[0], a[1], a[2], a[3], 0, None), 6, "null argument")
+        failed(L.kdlae_st_workspace_bytes(h, 2, 7, 30, 32), -1,
+               "B, F, H, W must be positive with H, W divisible by 2^(levels)")
+        failed(L.kdlae_st_forward(h, FAKE, FAKE, 2, 7, 30, 32, FAKE, FAKE, 0, None), 1,
+               "KDLAE_student needs H and W divisible by 2^(len(hidden_channels)-1)")
+        failed(L.kdlae_st_forward(h, FAKE, FAKE, 0, 7, 32, 32, FAKE, FAKE, 0, None), 1,
+               "KDLAE_student needs H and W divisible by 2^(len(hidden_channels)-1)")
+        failed(L.kdlae_st_forward(h, FAKE, FAKE, 1, 1, 32, 32, FAKE, FAKE, 0, None), 6, "training workspace too small")
+        failed(L.kdlae_st_backward(h, FAKE, FAKE, FAKE, FAKE, 0, None), 6,
+               "kdlae_st_backward needs a preceding kdlae_st_forward on the same workspace")
+    finally:
+        L.kdlae_st_destroy(h)
+    h2 = _st_handle((16, 30, 64))
+    failed(h2[3], 2, "KDLAE_student training on the HIP path needs hidden_channels divisible by 4 (inference takes any)")
+    assert h2[2].value is None
+
+
+# kdlae_st_workspace_bytes of commit e977bd4 (make_plan is host code): the bench student at its
+# training shape, and a 48-wide input, whose level 0 convs are planned direct and the deeper ones
+# (24 and 12 wide) through column matrices
+@pytest.mark.parametrize("shape,want", [((2, 4, 64, 64), 114273536), ((1, 3, 32, 48), 91882752)])
+def test_workspace_bytes_pinned(shape, want):
+    L, _, h, rc = _st_handle()
+    assert rc == 0
+    try:
+        assert L.kdlae_st_workspace_bytes(h, *shape) == want
+    finally:
+        L.kdlae_st_destroy(h)

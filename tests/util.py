@@ -31,3 +31,20 @@ def mdd_input_tensor(d):
 
 def max_abs(a, b):
     return float((a.double() - b.double()).abs().max())
+
+
+FAKE = 4096  # a non-null, 16-byte aligned "device pointer" for entries that must fail before they touch it
+
+
+def failed(rc, code, text):
+    """An entry point that refused: its KDLAE_E* code and the text it left in kdlae_last_error."""
+    from rethink_acoustic_image_enhancement_amd import _lib
+    assert (rc, _lib.last_error()) == (code, text), (rc, _lib.last_error())
+
+
+def silent(call, want):
+    """An entry point that answers `want` without touching kdlae_last_error."""
+    from rethink_acoustic_image_enhancement_amd import _lib
+    failed(_lib.lib().kdlae_train_ema(None, None, 0, 0.0, None), 2, "bad argument")
+    assert call() == want
+    assert _lib.last_error() == "bad argument"
