@@ -126,6 +126,41 @@ int64_t kdlae_t_workspace_bytes(const kdlae_t_handle* h, int B, int H, int W);
 int kdlae_t_forward(kdlae_t_handle* h, const float* img, const float* rate, int B, int H, int W,
                     float* hq, float* sr, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Rate sweep: R denoise rates of the same B images in one call.  Everything up to and including the
+ * `output` conv (KDLAE_model.py:275-314) sees only the image and runs once at batch B; its result is
+ * fanned out into R B rows that differ in the rate channel only, and output_param / refinement_out /
+ * output2 (+ the sr head when `sr` is given) run at batch R B.  Row r B + b is bit for bit what
+ * kdlae_t_forward gives for image b at rate r.
+ *   rates  DEVICE; rate_is_map == 0: [R][B] scalars, rate_is_map == 1: [R][B][1][H][W] maps
+ *   hq     [R][B][out_channels][H][W]    (hq[r] is a contiguous batch)
+ *   sr     [R][B][out_channels][2H][2W], or NULL to skip the sr head (allowed with static_train == 1;
+ *          non-NULL with static_train == 0 is KDLAE_EINVAL_CONFIG)
+ * Needs params_cat == 1 (else KDLAE_EINVAL_CONFIG), 1 <= R <= 64 and H % 8 == 0, W % 8 == 0 (else
+ * KDLAE_EINVAL_SHAPE); refused (KDLAE_ESTATE) while debug taps are armed.  Every check comes before the
+ * first launch.  kdlae_t_rates_workspace_bytes sizes the scratch: trunk buffers for B images, tail
+ * buffers for R B, the sr head's for R B only when with_sr. */
+int64_t kdlae_t_rates_workspace_bytes(const kdlae_t_handle* h, int B, int R, int H, int W, int with_sr);
+int kdlae_t_forward_rates(kdlae_t_handle* h, const float* img, const float* rates, int rate_is_map, int B, int R,
+                          int H, int W, float* hq, float* sr, void* workspace, int64_t workspace_bytes,
+                          void* stream);
+
+/* The sr head alone (cen -> upen -> enhance -> outputen, KDLAE_model.py:326-329) on a given UNclamped
+ * hq [B][out_channels][H][W] -> sr [B][out_channels][2H][2W]: the last four steps of kdlae_t_forward.
+ * static_train == 0: KDLAE_EINVAL_CONFIG. */
+int64_t kdlae_t_sr_workspace_bytes(const kdlae_t_handle* h, int B, int H, int W);
+int kdlae_t_forward_sr(kdlae_t_handle* h, const float* hq, int B, int H, int W, float* sr, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+
+/* Picks one of R candidates per image from device scores [R][B] and copies it out, without a host
+ * round trip: mode 0 = argmin_r |score[r][b] - target[b]| (target: device [B], fp32 arithmetic),
+ * mode 1 = argmax, mode 2 = argmin (target unused, may be NULL).  Ties go to the lowest r; a NaN score
+ * is never chosen, and index 0 is chosen when all R are NaN.  Writes index_out[b] (int32) and copies
+ * hq[index][b] (per_image floats; hq is [R][B][per_image]) into hq_out[b].  No atomics, so the result
+ * is a function of the inputs alone; any float alignment of hq / hq_out is accepted.  Null pointers,
+ * R, B or per_image < 1, or a mode outside 0..2: KDLAE_EINVAL_CONFIG before any launch. */
+int kdlae_rate_select(const float* scores, int R, int B, int mode, const float* target, const float* hq,
+                      int64_t per_image, int32_t* index_out, float* hq_out, void* stream);
+
 /* Measurement hook for bench.py (no effect on results).  When a probe class is armed, every
  * launch of that kernel class inside kdlae_t_forward is bracketed by a pair of HIP events on
  * `stream`; kdlae_t_probe_read synchronises those events and returns the summed device time (ms),

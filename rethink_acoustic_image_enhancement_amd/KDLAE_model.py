@@ -398,6 +398,97 @@ class KDLAE_teacher(nn.Module):
         _lib.check(rc, "kdlae_t_forward")
         return {"hq": hq, "sr": sr}
 
+    # ------------------------------------------------------------------ rate sweep
+    def _check_inference_input(self, x, what):
+        if self.dual_pixel_task:
+            raise NotImplementedError("dual_pixel_task=True: the reference forward leaves out_hq undefined "
+                                      "(KDLAE_model.py:305-321)")
+        if self.training:
+            raise RuntimeError(f"KDLAE_teacher.{what} is inference-only: call .eval() first (the training path "
+                               "differentiates through forward)")
+        if x.device.type != "cuda":
+            raise RuntimeError("KDLAE_teacher (MI355X build) runs on ROCm devices only; move the model "
+                               "inputs to 'cuda' — there is no CPU fallback")
+
+    def forward_rates(self, img, rates, sr=False):
+        """R denoise rates of the same images in one call: the rate-independent trunk (everything up to the
+        ``output`` conv) runs once, the rate-dependent tail at batch R*B (``kdlae_t_forward_rates``).
+
+        ``rates``: R scalars (sequence or 1-D tensor, shared by the batch), an ``[R, B]`` tensor, or
+        ``[R, B, 1, H, W]`` maps.  Returns ``{"hq": [R,B,C,H,W], "sr": [R,B,C,2H,2W] or None}``; ``hq[r]`` /
+        ``sr[r]`` are bit for bit what ``forward`` gives with ``denoise_rate = rates[r]``.  Eval mode, eager."""
+        self._check_inference_input(img, "forward_rates")
+        ci = self._cfg["inp_channels"]
+        if img.dim() != 4 or img.shape[1] != ci:
+            raise RuntimeError(f"expected img [B,{ci},H,W], got {tuple(img.shape)}")
+        B, _, H, W = img.shape
+        if H % 8 or W % 8:
+            raise RuntimeError(f"KDLAE_teacher needs H and W divisible by 8, got {H}x{W} "
+                               "(pad to a multiple of 8 as KDLAE_T.ipynb does)")
+        if self._cfg["params"] != "cat":
+            raise RuntimeError("forward_rates needs params='cat': with params='plus' the forward never reads "
+                               "denoise_rate")
+        if sr and self.static != "train":
+            raise RuntimeError("forward_rates(sr=True) needs static='train': the model has no sr head")
+        dev = img.device
+        rt = torch.as_tensor(rates, dtype=torch.float32).detach().to(dev)
+        if rt.dim() == 1:
+            rt = rt[:, None].expand(-1, B)
+        is_map = rt.dim() == 5
+        R = rt.shape[0] if rt.dim() else 0
+        if not (tuple(rt.shape) == (R, B) or tuple(rt.shape) == (R, B, 1, H, W)):
+            raise RuntimeError(f"rates must be R scalars, [R,B] or [R,B,1,H,W] with B,H,W = {B, H, W}, got "
+                               f"{tuple(rt.shape)}")
+        if not 1 <= R <= 64:
+            raise RuntimeError(f"forward_rates takes 1..64 rates, got {R}")
+        rt = rt.contiguous()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        eng = self.engine(dev)
+        eng.sync_params(self, stream)
+        img_c = img.detach().to(torch.float32).contiguous()
+        oc = self._cfg["out_channels"]
+        hq = torch.empty((R, B, oc, H, W), device=dev, dtype=torch.float32)
+        srt = torch.empty((R, B, oc, 2 * H, 2 * W), device=dev, dtype=torch.float32) if sr else None
+        L = _lib.lib()
+        nbytes = L.kdlae_t_rates_workspace_bytes(eng.handle, B, R, H, W, int(bool(sr)))
+        if nbytes < 0:
+            _lib.check(1, "kdlae_t_rates_workspace_bytes")
+        ws = eng.workspace(nbytes, dev)
+        rc = L.kdlae_t_forward_rates(eng.handle, ctypes.c_void_p(img_c.data_ptr()), ctypes.c_void_p(rt.data_ptr()),
+                                     int(is_map), B, R, H, W, ctypes.c_void_p(hq.data_ptr()),
+                                     ctypes.c_void_p(srt.data_ptr() if srt is not None else 0),
+                                     ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.c_void_p(stream))
+        _lib.check(rc, "kdlae_t_forward_rates")
+        return {"hq": hq, "sr": srt}
+
+    def forward_sr(self, hq):
+        """The sr head alone on an (unclamped) ``hq`` [B,C,H,W] -> ``sr`` [B,C,2H,2W]: the bits ``forward``
+        gives for the same ``hq``.  Needs static='train'.  Eval mode, eager."""
+        self._check_inference_input(hq, "forward_sr")
+        oc = self._cfg["out_channels"]
+        if hq.dim() != 4 or hq.shape[1] != oc:
+            raise RuntimeError(f"expected hq [B,{oc},H,W], got {tuple(hq.shape)}")
+        B, _, H, W = hq.shape
+        if H % 8 or W % 8:
+            raise RuntimeError(f"KDLAE_teacher needs H and W divisible by 8, got {H}x{W}")
+        if self.static != "train":
+            raise RuntimeError("forward_sr needs static='train': the model has no sr head")
+        dev = hq.device
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        eng = self.engine(dev)
+        eng.sync_params(self, stream)
+        hq_c = hq.detach().to(torch.float32).contiguous()
+        sr = torch.empty((B, oc, 2 * H, 2 * W), device=dev, dtype=torch.float32)
+        L = _lib.lib()
+        nbytes = L.kdlae_t_sr_workspace_bytes(eng.handle, B, H, W)
+        if nbytes < 0:
+            _lib.check(1, "kdlae_t_sr_workspace_bytes")
+        ws = eng.workspace(nbytes, dev)
+        rc = L.kdlae_t_forward_sr(eng.handle, ctypes.c_void_p(hq_c.data_ptr()), B, H, W, ctypes.c_void_p(sr.data_ptr()),
+                                  ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.c_void_p(stream))
+        _lib.check(rc, "kdlae_t_forward_sr")
+        return sr
+
 
 # BasicSR registers the same network under this name (Train/basicsr/models/archs/restormer_arch.py:566)
 RestormerSuperResolutionParam2 = KDLAE_teacher

@@ -25,6 +25,8 @@ EXPORTS = (
     "kdlae_t_create", "kdlae_t_destroy", "kdlae_t_num_params", "kdlae_t_param_info",
     "kdlae_t_set_param", "kdlae_t_commit_params", "kdlae_t_params_numel", "kdlae_t_prepare", "kdlae_t_pack_device",
     "kdlae_t_workspace_bytes", "kdlae_t_forward",
+    "kdlae_t_rates_workspace_bytes", "kdlae_t_forward_rates", "kdlae_t_sr_workspace_bytes", "kdlae_t_forward_sr",
+    "kdlae_rate_select",
     "kdlae_t_probe_arm", "kdlae_t_probe_read",
     "kdlae_t_debug_tap_count", "kdlae_t_debug_tap_info", "kdlae_t_debug_taps",
     "kdlae_s_create", "kdlae_s_destroy", "kdlae_s_num_params", "kdlae_s_param_info",
@@ -217,6 +219,15 @@ def lib() -> ctypes.CDLL:
     L.kdlae_t_workspace_bytes.restype = c_int64
     L.kdlae_t_forward.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                   c_void_p, c_int64, c_void_p]
+    L.kdlae_t_rates_workspace_bytes.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int]
+    L.kdlae_t_rates_workspace_bytes.restype = c_int64
+    L.kdlae_t_forward_rates.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                        c_void_p, c_void_p, c_int64, c_void_p]
+    L.kdlae_t_sr_workspace_bytes.argtypes = [c_void_p, c_int, c_int, c_int]
+    L.kdlae_t_sr_workspace_bytes.restype = c_int64
+    L.kdlae_t_forward_sr.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]
+    L.kdlae_rate_select.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                    c_void_p]
     L.kdlae_t_probe_arm.argtypes = [c_void_p, c_int, c_int]
     L.kdlae_t_probe_read.argtypes = [c_void_p, ctypes.POINTER(c_double), ctypes.POINTER(c_int64),
                                      ctypes.POINTER(c_double), ctypes.POINTER(c_double)]

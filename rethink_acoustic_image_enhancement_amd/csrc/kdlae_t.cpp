@@ -117,6 +117,7 @@ struct Stage {
   std::vector<BlockW> kdlae_t_handle::*blocks;
   bool packed;  // the module has it (its keys are in the state_dict): packed, and counted by make_plan
   bool runs;    // the forward runs it: refinement_out only for params == "cat", enhance only for static == "train"
+  int part;     // 0 trunk (sees only the image), 1 rate-dependent tail, 2 sr head: a rate sweep batches them apart
 };
 static std::vector<Stage> stages(const kdlae_t_config& c) {
   using H = kdlae_t_handle;
@@ -124,16 +125,16 @@ static std::vector<Stage> stages(const kdlae_t_config& c) {
   const int *nb = c.num_blocks, *hd = c.heads;
   const bool cat = c.params_cat != 0, sr = c.static_train != 0;
   return {
-      {"encoder_level1", nb[0], d, hd[0], 1, 1, &H::enc1, true, true},
-      {"encoder_level2", nb[1], 2 * d, hd[1], 1, 2, &H::enc2, true, true},
-      {"encoder_level3", nb[2], 4 * d, hd[2], 1, 4, &H::enc3, true, true},
-      {"latent", nb[3], 8 * d, hd[3], 1, 8, &H::latent, true, true},
-      {"decoder_level3", nb[2], 4 * d, hd[2], 1, 4, &H::dec3, true, true},
-      {"decoder_level2", nb[1], 2 * d, hd[1], 1, 2, &H::dec2, true, true},
-      {"decoder_level1", nb[0], 2 * d, hd[0], 1, 1, &H::dec1, true, true},
-      {"refinement", nr, 2 * d, hd[0], 1, 1, &H::refinement, true, true},
-      {"refinement_out", nr, 2 * d, hd[0], 1, 1, &H::refinement_out, true, cat},
-      {"enhance", nr, d, hd[0], 2, 1, &H::enhance, sr, sr},
+      {"encoder_level1", nb[0], d, hd[0], 1, 1, &H::enc1, true, true, 0},
+      {"encoder_level2", nb[1], 2 * d, hd[1], 1, 2, &H::enc2, true, true, 0},
+      {"encoder_level3", nb[2], 4 * d, hd[2], 1, 4, &H::enc3, true, true, 0},
+      {"latent", nb[3], 8 * d, hd[3], 1, 8, &H::latent, true, true, 0},
+      {"decoder_level3", nb[2], 4 * d, hd[2], 1, 4, &H::dec3, true, true, 0},
+      {"decoder_level2", nb[1], 2 * d, hd[1], 1, 2, &H::dec2, true, true, 0},
+      {"decoder_level1", nb[0], 2 * d, hd[0], 1, 1, &H::dec1, true, true, 0},
+      {"refinement", nr, 2 * d, hd[0], 1, 1, &H::refinement, true, true, 0},
+      {"refinement_out", nr, 2 * d, hd[0], 1, 1, &H::refinement_out, true, cat, 1},
+      {"enhance", nr, d, hd[0], 2, 1, &H::enhance, sr, sr, 2},
   };
 }
 
@@ -370,6 +371,7 @@ struct Packer {
 struct Plan : WsPlan {
   size_t catL1, catL2, catL3, lat, dec3, dec2, out4, refo, cenb, srs;
   size_t qkv, vbuf, fpre, fg, stats, part, red, Mp;
+  size_t out4t;  // rate sweep only
 };
 
 // Partial Gram slots per (image, head).  The slot partition depends on the image size only, never on
@@ -390,10 +392,14 @@ int nslots_for(int H, int W) {
   return std::max(1, std::min(64, n));
 }
 
-static Plan make_plan(const kdlae_t_handle* h, int B, int H, int W) {
+// Bn[part] = images each part of the network runs at (Stage::part): the forward runs all three at B; a rate
+// sweep runs the trunk at B and the tail (and the sr head, if asked for) at R B; the sr head alone has no
+// trunk and no tail.  fan: the sweep's B-image copy of the `output` conv that the fan-out kernel reads.
+static Plan make_plan(const kdlae_t_handle* h, const int (&Bn)[3], int H, int W, bool fan) {
   const kdlae_t_config& c = h->cfg;
   const long long d = c.dim;
-  const long long P1 = (long long)B * H * W, P2 = P1 / 4, P3 = P1 / 16, P4 = P1 / 64, Psr = 4 * P1;
+  const long long HW = (long long)H * W;
+  const long long P1 = Bn[0] * HW, P2 = P1 / 4, P3 = P1 / 16, P4 = P1 / 64, Pt = Bn[1] * HW, Ps = Bn[2] * HW;
   Plan pl;
   pl.catL1 = pl.take(P1 * 2 * d);
   pl.catL2 = pl.take(P2 * 4 * d);
@@ -401,15 +407,16 @@ static Plan make_plan(const kdlae_t_handle* h, int B, int H, int W) {
   pl.lat = pl.take(P4 * 8 * d);
   pl.dec3 = pl.take(P3 * 4 * d);
   pl.dec2 = pl.take(P2 * 2 * d);
-  pl.out4 = pl.take(P1 * 4);
-  pl.refo = pl.take(P1 * 2 * d);
-  pl.cenb = c.static_train ? pl.take(P1 * 2 * d) : 0;
-  pl.srs = c.static_train ? pl.take(Psr * d) : 0;
+  pl.out4 = pl.take(Pt * 4);
+  pl.refo = pl.take(Pt * 2 * d);
+  pl.cenb = c.static_train ? pl.take(Ps * 2 * d) : 0;
+  pl.srs = c.static_train ? pl.take(4 * Ps * d) : 0;
   // per-block scratch: max over every packed stage (refinement_out too when the forward skips it)
   long long mq = 0, mv = 0, mfp = 0, mfg = 0, mst = 0, mpart = 0, mred = 0, mM = 0;
   for (const Stage& st : stages(c)) {
     const int Hh = H * st.num / st.den, Ww = W * st.num / st.den;
-    const long long P = (long long)B * Hh * Ww;
+    const long long Bs = Bn[st.part];
+    const long long P = Bs * Hh * Ww;
     for (const BlockW& b : h->*st.blocks) {
       const long long slot = gram_slot_floats(b.Ch);
       mq = std::max(mq, P * 3 * b.C);
@@ -417,9 +424,9 @@ static Plan make_plan(const kdlae_t_handle* h, int B, int H, int W) {
       mfp = std::max(mfp, P * 2 * b.hidS);
       if (!b.fused_gdfn) mfg = std::max(mfg, P * b.hidS);  // gated tensor: unfused FFN tails only
       mst = std::max(mst, P * 2);
-      mpart = std::max(mpart, (long long)B * b.heads * nslots_for(Hh, Ww) * slot);
-      mred = std::max(mred, (long long)B * b.heads * slot);
-      mM = std::max(mM, (long long)B * folded_proj_floats(b.C));
+      mpart = std::max(mpart, Bs * b.heads * nslots_for(Hh, Ww) * slot);
+      mred = std::max(mred, Bs * b.heads * slot);
+      mM = std::max(mM, Bs * folded_proj_floats(b.C));
     }
   }
   pl.qkv = pl.take(mq);
@@ -430,8 +437,10 @@ static Plan make_plan(const kdlae_t_handle* h, int B, int H, int W) {
   pl.part = pl.take(mpart);
   pl.red = pl.take(mred);
   pl.Mp = pl.take(mM);
+  pl.out4t = fan ? pl.take(P1 * 4) : 0;
   return pl;
 }
+static Plan make_plan(const kdlae_t_handle* h, int B, int H, int W) { return make_plan(h, {B, B, B}, H, W, false); }
 
 // ----------------------------------------------------------------------------- forward
 struct Fwd {
@@ -831,7 +840,9 @@ struct Fwd {
     return KDLAE_OK;
   }
 
-  int run(const float* img, const float* rate, int H, int W, float* hq, float* sr) {
+  // The part of the forward that sees only the image (:275-302): patch_embed .. refinement, left in the
+  // level-1 concat buffer (2 dim channels).
+  int trunk(const float* img, int H, int W) {
     const kdlae_t_config& c = h->cfg;
     const int d = c.dim;
     int rc;
@@ -865,29 +876,71 @@ struct Fwd {
     if ((rc = gemm(h->up2_1, h->P3(h->up2_1.w3), 0, d2, H2, W2, View{L1, 2 * d}, 2, nullptr, 0, 0, 0, -1))) return rc;
     View d1{L1, 2 * d};
     if ((rc = stage(h->dec1, d1, H, W))) return rc;
-    if ((rc = stage(h->refinement, d1, H, W))) return rc;
-    const int co = c.out_channels;
+    return stage(h->refinement, d1, H, W);
+  }
+
+  // cat[out, denoise_rate] in the NHWC-4 buffer pl.out4 -> output_param dil 2 (:317) -> refinement_out, left in pl.refo
+  int rate_tail(int H, int W) {
+    const long long HW = (long long)H * W;
+    int rc;
+    View ro{buf(pl.refo), 2 * h->cfg.dim};
+    if ((rc = small_in(h->output_param, buf(pl.out4), 4 * HW, 1, 4LL * W, 4, H, W, ro, 2))) return rc;
+    return stage(h->refinement_out, ro, H, W);
+  }
+
+  // sr head on the UNclamped hq (:326-329)
+  int sr_head(const float* hq, int H, int W, float* sr) {
+    const int d = h->cfg.dim, co = h->cfg.out_channels;
+    const long long HW = (long long)H * W;
+    int rc;
+    View cb{buf(pl.cenb), 2 * d};
+    if ((rc = small_in(h->cen, hq, co * HW, HW, W, 1, H, W, cb, 1))) return rc;
+    View sv{buf(pl.srs), d};
+    if ((rc = gemm(h->upen, h->P3(h->upen.w3), 0, cb, H, W, sv, 2, nullptr, 0, 0, 0, -1))) return rc;
+    if ((rc = stage(h->enhance, sv, 2 * H, 2 * W))) return rc;
+    return small_out(h->outputen, sv, 2 * H, 2 * W, sr, 1, 0, nullptr, nullptr);
+  }
+
+  int run(const float* img, const float* rate, int H, int W, float* hq, float* sr) {
+    const kdlae_t_config& c = h->cfg;
+    const int d = c.dim;
+    int rc;
+    if ((rc = trunk(img, H, W))) return rc;
+    View d1{buf(pl.catL1), 2 * d};
     if (c.params_cat) {
-      // output (:314) + cat denoise_rate (:316) -> output_param dil 2 (:317) -> refinement_out -> output2 + img
-      float* o4 = buf(pl.out4);
-      if ((rc = small_out(h->output, d1, H, W, o4, 0, 4, nullptr, rate))) return rc;
-      View ro{buf(pl.refo), 2 * d};
-      if ((rc = small_in(h->output_param, o4, 4 * HW, 1, 4LL * W, 4, H, W, ro, 2))) return rc;
-      if ((rc = stage(h->refinement_out, ro, H, W))) return rc;
-      if ((rc = small_out(h->output2, ro, H, W, hq, 1, 0, img, nullptr))) return rc;
+      // output (:314) + cat denoise_rate (:316) -> output_param -> refinement_out -> output2 + img
+      if ((rc = small_out(h->output, d1, H, W, buf(pl.out4), 0, 4, nullptr, rate))) return rc;
+      if ((rc = rate_tail(H, W))) return rc;
+      if ((rc = small_out(h->output2, View{buf(pl.refo), 2 * d}, H, W, hq, 1, 0, img, nullptr))) return rc;
     } else {
       if ((rc = small_out(h->output, d1, H, W, hq, 1, 0, img, nullptr))) return rc;
     }
-    if (c.static_train) {
-      // sr head on the UNclamped hq (:326-329)
-      View cb{buf(pl.cenb), 2 * d};
-      if ((rc = small_in(h->cen, hq, co * HW, HW, W, 1, H, W, cb, 1))) return rc;
-      View sv{buf(pl.srs), d};
-      if ((rc = gemm(h->upen, h->P3(h->upen.w3), 0, cb, H, W, sv, 2, nullptr, 0, 0, 0, -1))) return rc;
-      if ((rc = stage(h->enhance, sv, 2 * H, 2 * W))) return rc;
-      if ((rc = small_out(h->outputen, sv, 2 * H, 2 * W, sr, 1, 0, nullptr, nullptr))) return rc;
-    }
+    if (c.static_train) return sr_head(hq, H, W, sr);
     return KDLAE_OK;
+  }
+
+  // kdlae_t_forward_rates: the trunk and the `output` conv once at batch B (this->B), the fan-out of its
+  // NHWC-4 result over the R rates, then the tail (and the sr head) at batch R B.  output2 adds img[b] to
+  // row r B + b: one launch per rate at batch B, each on its own slice of pl.refo and hq.
+  int run_rates(const float* img, const float* rates, int is_map, int R, int H, int W, float* hq, float* sr) {
+    const kdlae_t_config& c = h->cfg;
+    const int d = c.dim, co = c.out_channels, Bimg = B;
+    const long long HW = (long long)H * W;
+    int rc;
+    if ((rc = trunk(img, H, W))) return rc;
+    if ((rc = small_out(h->output, View{buf(pl.catL1), 2 * d}, H, W, buf(pl.out4t), 0, 4, nullptr, nullptr))) return rc;
+    HIPCHK(launch_rate_fanout(buf(pl.out4t), rates, is_map, co, Bimg, R, HW, buf(pl.out4), s));
+    B = R * Bimg;
+    if ((rc = rate_tail(H, W))) return rc;
+    B = Bimg;
+    for (int r = 0; r < R; ++r) {
+      const long long row0 = (long long)r * Bimg * HW;
+      if ((rc = small_out(h->output2, View{buf(pl.refo) + row0 * 2 * d, 2 * d}, H, W, hq + row0 * co, 1, 0, img, nullptr)))
+        return rc;
+    }
+    if (!sr) return KDLAE_OK;
+    B = R * Bimg;
+    return sr_head(hq, H, W, sr);
   }
 };
 
@@ -1003,6 +1056,86 @@ int kdlae_t_forward(kdlae_t_handle* h, const float* img, const float* rate, int 
   if ((int64_t)f.pl.total > workspace_bytes) return fail(KDLAE_ESTATE, "workspace too small");
   DeviceGuard g(h->device);
   return f.run(img, rate, H, W, hq, sr);
+}
+
+// What a rate sweep's arguments must satisfy apart from the pointers (kdlae_t_forward_rates and its
+// workspace query): nothing here needs the packed parameters.
+static int check_rates(const kdlae_t_handle* h, int B, int R, int H, int W, bool with_sr) {
+  if (R < 1 || R > 64) return fail(KDLAE_EINVAL_SHAPE, "a rate sweep takes 1 <= R <= 64 rates, got " + std::to_string(R));
+  if (B <= 0 || H <= 0 || W <= 0 || H % 8 || W % 8)
+    return fail(KDLAE_EINVAL_SHAPE, "KDLAE_teacher needs H % 8 == 0 and W % 8 == 0 (pixel_unshuffle x3, KDLAE_model.py:187)");
+  if ((long long)R * B > 0x7fffffffLL / ((long long)H * W))
+    return fail(KDLAE_EINVAL_SHAPE, "R * B * H * W must stay below 2^31 pixels");
+  if (!h->cfg.params_cat)
+    return fail(KDLAE_EINVAL_CONFIG, "a rate sweep needs params=='cat': with params=='plus' the forward never reads denoise_rate");
+  if (with_sr && !h->cfg.static_train)
+    return fail(KDLAE_EINVAL_CONFIG, "sr asked for, but static != 'train': the model has no sr head");
+  return KDLAE_OK;
+}
+
+static bool taps_armed(const kdlae_t_handle* h) {
+  return std::any_of(h->taps.begin(), h->taps.end(), [](const float* p) { return p != nullptr; });
+}
+
+int64_t kdlae_t_rates_workspace_bytes(const kdlae_t_handle* h, int B, int R, int H, int W, int with_sr) {
+  if (!h) {
+    fail(KDLAE_ESTATE, "null handle");
+    return -1;
+  }
+  if (check_rates(h, B, R, H, W, with_sr != 0)) return -1;
+  if (!h->committed) {
+    fail(KDLAE_ESTATE, "workspace_bytes needs committed params");
+    return -1;
+  }
+  return (int64_t)make_plan(h, {B, R * B, with_sr ? R * B : 0}, H, W, true).total;
+}
+
+int kdlae_t_forward_rates(kdlae_t_handle* h, const float* img, const float* rates, int rate_is_map, int B, int R,
+                          int H, int W, float* hq, float* sr, void* workspace, int64_t workspace_bytes,
+                          void* stream) {
+  if (!h) return fail(KDLAE_ESTATE, "null handle");
+  if (!img || !rates || !hq) return fail(KDLAE_ESTATE, "img, rates and hq are required");
+  if (rate_is_map != 0 && rate_is_map != 1) return fail(KDLAE_EINVAL_CONFIG, "rate_is_map must be 0 or 1");
+  int rc = check_rates(h, B, R, H, W, sr != nullptr);
+  if (rc) return rc;
+  if (!h->committed) return fail(KDLAE_ESTATE, "forward before kdlae_t_commit_params / kdlae_t_pack_device");
+  if (taps_armed(h)) return fail(KDLAE_ESTATE, "debug taps are sized for kdlae_t_forward: disarm them before a rate sweep");
+  Fwd f{h, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<char*>(workspace),
+        make_plan(h, {B, R * B, sr ? R * B : 0}, H, W, true), B};
+  if (!workspace || (int64_t)f.pl.total > workspace_bytes) return fail(KDLAE_ESTATE, "workspace too small");
+  DeviceGuard g(h->device);
+  return f.run_rates(img, rates, rate_is_map, R, H, W, hq, sr);
+}
+
+int64_t kdlae_t_sr_workspace_bytes(const kdlae_t_handle* h, int B, int H, int W) {
+  if (!h || !h->committed) {
+    fail(KDLAE_ESTATE, "workspace_bytes needs committed params");
+    return -1;
+  }
+  if (B <= 0 || H <= 0 || W <= 0 || H % 8 || W % 8) {
+    fail(KDLAE_EINVAL_SHAPE, "B, H, W must be positive with H % 8 == 0 and W % 8 == 0");
+    return -1;
+  }
+  if (!h->cfg.static_train) {
+    fail(KDLAE_EINVAL_CONFIG, "static != 'train': the model has no sr head");
+    return -1;
+  }
+  return (int64_t)make_plan(h, {0, 0, B}, H, W, false).total;
+}
+
+int kdlae_t_forward_sr(kdlae_t_handle* h, const float* hq, int B, int H, int W, float* sr, void* workspace,
+                       int64_t workspace_bytes, void* stream) {
+  if (!h) return fail(KDLAE_ESTATE, "null handle");
+  if (!hq || !sr) return fail(KDLAE_ESTATE, "hq and sr are required");
+  if (B <= 0 || H <= 0 || W <= 0 || H % 8 || W % 8)
+    return fail(KDLAE_EINVAL_SHAPE, "KDLAE_teacher needs H % 8 == 0 and W % 8 == 0 (pixel_unshuffle x3, KDLAE_model.py:187)");
+  if (!h->cfg.static_train) return fail(KDLAE_EINVAL_CONFIG, "static != 'train': the model has no sr head");
+  if (!h->committed) return fail(KDLAE_ESTATE, "forward before kdlae_t_commit_params / kdlae_t_pack_device");
+  if (taps_armed(h)) return fail(KDLAE_ESTATE, "debug taps are sized for kdlae_t_forward: disarm them before kdlae_t_forward_sr");
+  Fwd f{h, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<char*>(workspace), make_plan(h, {0, 0, B}, H, W, false), B};
+  if (!workspace || (int64_t)f.pl.total > workspace_bytes) return fail(KDLAE_ESTATE, "workspace too small");
+  DeviceGuard g(h->device);
+  return f.sr_head(hq, H, W, sr);
 }
 
 // The debug taps in the order kdlae_t_forward passes them: per stage that runs, its input, then per

@@ -130,6 +130,10 @@ hipError_t launch_conv_small_out(const SmallOutParams& p, hipStream_t s);
 // MaxPool (1,2,2) / MaxPool2d(2) on NHWC views: [N frames][H][W][C] -> [N][H/2][W/2][C] (floor)
 hipError_t launch_maxpool2(const float* in, int ldi, float* out, int ldo, int C, long long nframes, int H, int W,
                            hipStream_t s);
+// Rate sweep fan-out (rates.hip): src = B NHWC-4 images, dst = R B NHWC-4 images, dst row (r B + b) = src row
+// b with channel `ch` replaced by the rate of (r, b): rates[r B + b], or with is_map rates[(r B + b) HW + pixel]
+hipError_t launch_rate_fanout(const float* src, const float* rates, int is_map, int ch, int B, int R, long long HW,
+                              float* dst, hipStream_t s);
 
 // Fused GDFN tail: out = R + project_out(gelu_erf(dw3x3(x1)) * dw3x3(x2)) (gdfn.hip).
 struct GdfnParams {

@@ -5,6 +5,10 @@
   multiple of 8, constant ``denoise_rate`` map, forward, then clamp / crop / ``img_as_ubyte`` and the
   zero-mask of input-black pixels (x2 nearest for ``sr``).  Pre and post are HIP kernels
   (``kdlae_preprocess_u8`` / ``kdlae_postprocess_u8``); images never round-trip through the host.
+* ``enhance_rates_u8`` / ``enhance_auto_u8`` — the notebook's "pick a rate, look, pick again" loop as one
+  call: R rates of the same images through ``KDLAE_teacher.forward_rates`` (the rate-independent trunk runs
+  once), every candidate post-processed as the notebook saves it, and — ``enhance_auto_u8`` — scored by
+  ASDQE against the input and the candidate picked per image on the device (``kdlae_rate_select``).
 * ``frames_preprocess_u8`` / ``enhance_frames_u8`` — KDLAE/KDLAE-S.ipynb's cell: F frames (gray or
   cv2 BGR/BGRA u8) -> COLOR_BGR2GRAY -> /255 -> [B,F,H,W] reflect-padded to a multiple of 32 ->
   KDLAE_student -> clamp / crop / permute to [h,w,F] / ``img_as_ubyte``, pre and post on the GPU.
@@ -76,6 +80,94 @@ def enhance_u8(model, images: torch.Tensor, denoise_rate, bgr: bool = False, mul
     hq = postprocess_u8(pred["hq"], h, w, 1, images)
     sr = postprocess_u8(pred["sr"], h, w, 2, images) if pred.get("sr") is not None else None
     return hq, sr
+
+
+def _rates_rb(rates, B: int, dev) -> torch.Tensor:
+    """R scalars (shared by the batch) or [R, B] -> contiguous f32 [R, B] on ``dev``."""
+    rt = torch.as_tensor(rates, dtype=torch.float32).to(dev)
+    if rt.dim() == 1:
+        rt = rt[:, None].expand(-1, B)
+    if rt.dim() != 2 or rt.shape[1] != B:
+        raise RuntimeError(f"rates must be R scalars or [R,{B}], got {tuple(rt.shape)}")
+    return rt.contiguous()
+
+
+def _sweep_u8(model, images: torch.Tensor, rates, bgr: bool, multiple: int):
+    B, h, w, _ = images.shape
+    img, _ = preprocess_u8(images, None, multiple, bgr)
+    rt = _rates_rb(rates, B, images.device)
+    with torch.no_grad():
+        hq = model.forward_rates(img, rt, sr=False)["hq"]
+    cands = torch.stack([postprocess_u8(hq[r], h, w, 1, images) for r in range(rt.shape[0])])
+    return rt, hq, cands
+
+
+def enhance_rates_u8(model, images: torch.Tensor, rates, bgr: bool = False, multiple: int = 8) -> torch.Tensor:
+    """``enhance_u8``'s hq for every rate of a sweep: u8 [B,h,w,C], R rates (scalars or [R,B]) -> u8 [R,B,h,w,C].
+    Candidate r is byte for byte ``enhance_u8(model, images, rates[r])[0]``."""
+    return _sweep_u8(model, images, rates, bgr, multiple)[2]
+
+
+_SELECT_MODES = {"closest": 0, "max": 1, "min": 2}
+
+
+def rate_select(scores: torch.Tensor, hq: torch.Tensor, select: str = "closest", target=None):
+    """``kdlae_rate_select``: device scores [R,B] and candidates [R,B,...] (f32) -> (index i32 [B], chosen [B,...]).
+    ``closest``: argmin |score - target| (target a float or [B]); ``max`` / ``min``: argmax / argmin.  Ties go to
+    the lowest r, a NaN score is never chosen.  No host synchronisation."""
+    if select not in _SELECT_MODES:
+        raise RuntimeError(f"select must be one of {sorted(_SELECT_MODES)}, got {select!r}")
+    if scores.device.type != "cuda" or hq.device != scores.device or scores.dim() != 2 or hq.dim() < 3 or \
+            tuple(hq.shape[:2]) != tuple(scores.shape):
+        raise RuntimeError("rate_select expects cuda scores [R,B] and candidates [R,B,...] on the same device")
+    R, B = scores.shape
+    dev = scores.device
+    scores = scores.detach().to(torch.float32).contiguous()
+    hq = hq.detach().to(torch.float32).contiguous()
+    tgt = None
+    if select == "closest":
+        if target is None:
+            raise RuntimeError("select='closest' needs a target score")
+        tgt = torch.as_tensor(target, dtype=torch.float32).to(dev).expand(B).contiguous()
+    index = torch.empty((B,), device=dev, dtype=torch.int32)
+    out = torch.empty(hq.shape[1:], device=dev, dtype=torch.float32)
+    rc = _lib.lib().kdlae_rate_select(
+        ctypes.c_void_p(scores.data_ptr()), R, B, _SELECT_MODES[select],
+        ctypes.c_void_p(tgt.data_ptr() if tgt is not None else 0), ctypes.c_void_p(hq.data_ptr()),
+        hq[0, 0].numel(), ctypes.c_void_p(index.data_ptr()), ctypes.c_void_p(out.data_ptr()), _stream(dev))
+    _lib.check(rc, "kdlae_rate_select")
+    return index, out
+
+
+def enhance_auto_u8(model, scorer, images: torch.Tensor, rates, target=None, select: str = "closest",
+                    want_sr: bool = False, bgr: bool = False) -> dict:
+    """Sweep ``rates`` over u8 images [B,h,w,C], score every post-processed candidate against its input with
+    ASDQE (``scorer``: a DenoiseRatePredictor in eval mode) and keep, per image, the candidate ``select``
+    names.  ``scores[r]`` is what ``asdqe_scores(scorer, images, enhance_rates_u8(...)[r])`` gives; the sr head
+    runs only on the chosen float hq, and only with ``want_sr``.  Everything stays on the device, with one
+    synchronisation before the results are returned:
+    ``{"hq": u8 [B,h,w,C], "rate": f32 [B], "index": i32 [B], "scores": f32 [R,B], "sr": u8 [B,2h,2w,C] | None}``."""
+    if select not in _SELECT_MODES:
+        raise RuntimeError(f"select must be one of {sorted(_SELECT_MODES)}, got {select!r}")
+    B, h, w, _ = images.shape
+    dev = images.device
+    rt, hq, cands = _sweep_u8(model, images, rates, bgr, 8)
+    R = rt.shape[0]
+    scores = torch.empty((R, B), device=dev, dtype=torch.float32)
+    with torch.no_grad():
+        for c0 in range(0, B, 64):  # asdqe_scores' chunking: every pair is scored independently
+            lq = to_tensor_u8(images[c0:c0 + 64])
+            for r in range(R):
+                scores[r, c0:c0 + 64] = scorer(lq, to_tensor_u8(cands[r, c0:c0 + 64])).view(-1)
+    index, hq_sel = rate_select(scores, hq, select, target)
+    pick = (index.long(), torch.arange(B, device=dev))
+    sr = None
+    if want_sr:
+        with torch.no_grad():
+            sr = postprocess_u8(model.forward_sr(hq_sel), h, w, 2, images)
+    out = {"hq": cands[pick], "rate": rt[pick], "index": index, "scores": scores, "sr": sr}
+    torch.cuda.current_stream(dev).synchronize()
+    return out
 
 
 def frames_preprocess_u8(frames: torch.Tensor, multiple: int = 32) -> torch.Tensor:
