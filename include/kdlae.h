@@ -23,7 +23,10 @@
  * the same bits: "no_attn_in_fusion" keeps the attention-output GEMM and the
  * LN + ffn.project_in GEMM separate (every block); "no_attn_in_split" keeps
  * them separate for the C = 96 blocks only (by default their first
- * project_in weight group is fused as well).  KDLAE_PROBE_DUMP
+ * project_in weight group is fused as well).  One flag selects between two
+ * evaluation orders that agree to fp32 rounding, not to the bit: "no_sr_fold"
+ * keeps the sr head's cen and upen convs as two launches instead of the one
+ * composed 5x5 conv (csrc/sr_fold.hip).  KDLAE_PROBE_DUMP
  * names a CSV file kdlae_t_probe_read writes per-launch timings to.
  * One more KDLAE_DEBUG flag is read on EVERY training call (kdlae_tt_forward /
  * kdlae_tt_backward / kdlae_tt_backward_marked), not at pack time:
@@ -144,7 +147,8 @@ int kdlae_t_forward_rates(kdlae_t_handle* h, const float* img, const float* rate
                           int H, int W, float* hq, float* sr, void* workspace, int64_t workspace_bytes,
                           void* stream);
 
-/* The sr head alone (cen -> upen -> enhance -> outputen, KDLAE_model.py:326-329) on a given UNclamped
+/* The sr head alone (cen -> upen -> enhance -> outputen, KDLAE_model.py:326-329; cen and upen run as one
+ * composed 5x5 conv) on a given UNclamped
  * hq [B][out_channels][H][W] -> sr [B][out_channels][2H][2W]: the last four steps of kdlae_t_forward.
  * static_train == 0: KDLAE_EINVAL_CONFIG. */
 int64_t kdlae_t_sr_workspace_bytes(const kdlae_t_handle* h, int B, int H, int W);
@@ -181,6 +185,13 @@ int kdlae_t_probe_read(kdlae_t_handle* h, double* ms, int64_t* launches, double*
 int kdlae_t_debug_tap_count(const kdlae_t_handle* h);
 int kdlae_t_debug_tap_info(const kdlae_t_handle* h, int i, char* name, int name_len, int* C, int* num, int* den);
 int kdlae_t_debug_taps(kdlae_t_handle* h, int n, float* const* dst);
+
+/* Diagnostics (tests/test_sr_fold_gpu.py): the sr head's folded-conv record as the last pack left it,
+ * [9 border classes][out_tiles = 8 dim / 16][ksteps = (25 out_channels + 4) / 4][64 lanes] floats (layout:
+ * csrc/pack.hip, pack_fold_kernel), copied into the device buffer dst on `stream`.  Returns the record's
+ * float count (dst == NULL: the count alone), 0 when the handle runs the unfolded sr head (static != 'train'
+ * or KDLAE_DEBUG=no_sr_fold), -1 on error. */
+int64_t kdlae_t_debug_sr_fold(const kdlae_t_handle* h, float* dst, int64_t capacity, void* stream);
 
 /* ------------------------------------------------------------------ KDLAE-S
  * Ctor kwargs of KDLAE_student (KDLAE/KDLAE_model.py:340-384): a 3-D U-Net over a burst of frames.

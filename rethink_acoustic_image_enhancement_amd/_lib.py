@@ -28,7 +28,7 @@ EXPORTS = (
     "kdlae_t_rates_workspace_bytes", "kdlae_t_forward_rates", "kdlae_t_sr_workspace_bytes", "kdlae_t_forward_sr",
     "kdlae_rate_select",
     "kdlae_t_probe_arm", "kdlae_t_probe_read",
-    "kdlae_t_debug_tap_count", "kdlae_t_debug_tap_info", "kdlae_t_debug_taps",
+    "kdlae_t_debug_tap_count", "kdlae_t_debug_tap_info", "kdlae_t_debug_taps", "kdlae_t_debug_sr_fold",
     "kdlae_s_create", "kdlae_s_destroy", "kdlae_s_num_params", "kdlae_s_param_info",
     "kdlae_s_set_param", "kdlae_s_commit_params", "kdlae_s_params_numel", "kdlae_s_prepare", "kdlae_s_pack_device",
     "kdlae_s_workspace_bytes", "kdlae_s_forward",
@@ -235,6 +235,8 @@ def lib() -> ctypes.CDLL:
     L.kdlae_t_debug_tap_info.argtypes = [c_void_p, c_int, c_char_p, c_int, ctypes.POINTER(c_int),
                                          ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
     L.kdlae_t_debug_taps.argtypes = [c_void_p, c_int, ctypes.POINTER(c_void_p)]
+    L.kdlae_t_debug_sr_fold.argtypes = [c_void_p, c_void_p, c_int64, c_void_p]
+    L.kdlae_t_debug_sr_fold.restype = c_int64
     L.kdlae_s_create.argtypes = [ctypes.POINTER(SConfig), c_int, ctypes.POINTER(c_void_p)]
     L.kdlae_s_destroy.argtypes = [c_void_p]
     L.kdlae_s_num_params.argtypes = [c_void_p]

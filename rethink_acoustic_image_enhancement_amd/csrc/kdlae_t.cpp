@@ -6,7 +6,8 @@
 //   buffer, so torch.cat at :299 is free) -> down1_2 (implicit-GEMM 3x3 + PixelUnshuffle store) ->
 //   ... -> latent -> up4_3 (3x3 + PixelShuffle store into the first half of the level-3 concat
 //   buffer, :288-289) -> reduce_chan_level3 -> ... -> output / output_param / refinement_out /
-//   output2 + img -> hq; static=="train": cen -> upen -> enhance -> outputen -> sr (:324-329).
+//   output2 + img -> hq; static=="train": [cen . upen as one 5x5 conv + PixelShuffle store, sr_fold.hip] ->
+//   enhance -> outputen -> sr (:324-329).
 // Each TransformerBlock (:159-163) is 7 launches:
 //   [LN1+qkv GEMM] [dwconv+Gram] [slot reduce] [softmax+fold into W_proj] [A.v.proj GEMM + residual]
 //   [LN2+project_in GEMM] [dwconv+GELU gate] [project_out GEMM + residual]   (+ LN stats when K is chunked)
@@ -60,6 +61,9 @@ struct kdlae_t_handle : HandleBase {
   SmallW patch_embed, output, output_param, output2, cen, outputen;
   Gemm down1_2, down2_3, down3_4, up4_3, up3_2, up2_1, upen, reduce3, reduce2;
   size_t zeros = kNone;  // 64 zero floats (halo source for the fused GDFN kernel)
+  // cen and upen composed into one 5x5 conv (sr_fold.hip; the record is a PFold of the pack program); debug
+  // flag no_sr_fold keeps the cen + upen launches (A/B baseline and reference), which are packed only then
+  size_t sr_fold = kNone;
   // probe
   int probe_class = 0, probe_level = 0;
   std::vector<hipEvent_t> ev;
@@ -409,7 +413,7 @@ static Plan make_plan(const kdlae_t_handle* h, const int (&Bn)[3], int H, int W,
   pl.dec2 = pl.take(P2 * 2 * d);
   pl.out4 = pl.take(Pt * 4);
   pl.refo = pl.take(Pt * 2 * d);
-  pl.cenb = c.static_train ? pl.take(Ps * 2 * d) : 0;
+  pl.cenb = c.static_train && h->sr_fold == kNone ? pl.take(Ps * 2 * d) : 0;  // cen's output: unfolded sr head only
   pl.srs = c.static_train ? pl.take(4 * Ps * d) : 0;
   // per-block scratch: max over every packed stage (refinement_out too when the forward skips it)
   long long mq = 0, mv = 0, mfp = 0, mfg = 0, mst = 0, mpart = 0, mred = 0, mM = 0;
@@ -893,10 +897,25 @@ struct Fwd {
     const int d = h->cfg.dim, co = h->cfg.out_channels;
     const long long HW = (long long)H * W;
     int rc;
-    View cb{buf(pl.cenb), 2 * d};
-    if ((rc = small_in(h->cen, hq, co * HW, HW, W, 1, H, W, cb, 1))) return rc;
     View sv{buf(pl.srs), d};
-    if ((rc = gemm(h->upen, h->P3(h->upen.w3), 0, cb, H, W, sv, 2, nullptr, 0, 0, 0, -1))) return rc;
+    if (h->sr_fold != kNone) {
+      // cen . upen as one 5x5 conv with border-class weights, PixelShuffle store (sr_fold.hip)
+      SrFoldParams q{};
+      q.in = hq;
+      q.Cin = co;
+      q.w = h->P(h->sr_fold);
+      q.ntiles = 4 * d / 16;
+      q.out = sv.p;
+      q.ldo = sv.ld;
+      q.Bn = B;
+      q.H = H;
+      q.W = W;
+      HIPCHK(launch_sr_fold(q, s));
+    } else {
+      View cb{buf(pl.cenb), 2 * d};
+      if ((rc = small_in(h->cen, hq, co * HW, HW, W, 1, H, W, cb, 1))) return rc;
+      if ((rc = gemm(h->upen, h->P3(h->upen.w3), 0, cb, H, W, sv, 2, nullptr, 0, 0, 0, -1))) return rc;
+    }
     if ((rc = stage(h->enhance, sv, 2 * H, 2 * W))) return rc;
     return small_out(h->outputen, sv, 2 * H, 2 * W, sr, 1, 0, nullptr, nullptr);
   }
@@ -1011,8 +1030,19 @@ static int record_program(HandleBase* base, PackProgram& prog) {
   h->output2 = pk.small("output2", c.out_channels, 2 * d, c.bias);
   if (c.static_train) {
     const int hc = 2 * d;
-    h->cen = pk.small("cen", hc, c.out_channels, c.bias);
-    h->upen = pk.conv3("upen.body.0", 2 * hc, hc, 2);
+    if (sr_fold_supported(c.out_channels, 2 * hc / 16) && !debug_flag("no_sr_fold")) {
+      PFold& f = prog.fold;
+      f.U = pk.get("upen.body.0.weight");
+      f.Cw = pk.get("cen.weight");
+      f.Cb = c.bias ? pk.get("cen.bias") : -1;
+      f.hc = hc;
+      f.cin = c.out_channels;
+      if (!pk.err) h->sr_fold = prog.add(std::vector<PEx>((size_t)f.floats()));
+      f.dst = pk.err ? -1 : (int64_t)h->sr_fold;
+    } else {
+      h->cen = pk.small("cen", hc, c.out_channels, c.bias);
+      h->upen = pk.conv3("upen.body.0", 2 * hc, hc, 2);
+    }
     h->outputen = pk.small("outputen", c.out_channels, hc / 2, c.bias);
   }
   for (const Stage& st : stages(c))
@@ -1136,6 +1166,27 @@ int kdlae_t_forward_sr(kdlae_t_handle* h, const float* hq, int B, int H, int W, 
   if (!workspace || (int64_t)f.pl.total > workspace_bytes) return fail(KDLAE_ESTATE, "workspace too small");
   DeviceGuard g(h->device);
   return f.sr_head(hq, H, W, sr);
+}
+
+int64_t kdlae_t_debug_sr_fold(const kdlae_t_handle* h, float* dst, int64_t capacity, void* stream) {
+  if (!h || !h->committed) {
+    fail(KDLAE_ESTATE, "kdlae_t_debug_sr_fold needs committed params");
+    return -1;
+  }
+  if (h->sr_fold == kNone) return 0;
+  const int64_t n = h->dw.fold.floats();
+  if (!dst) return n;
+  if (capacity < n) {
+    fail(KDLAE_EPARAM, "kdlae_t_debug_sr_fold: dst too small");
+    return -1;
+  }
+  DeviceGuard g(h->device);
+  if (hipMemcpyAsync(dst, h->P(h->sr_fold), (size_t)n * sizeof(float), hipMemcpyDeviceToDevice,
+                     reinterpret_cast<hipStream_t>(stream)) != hipSuccess) {
+    fail(KDLAE_EHIP, "kdlae_t_debug_sr_fold: copy failed");
+    return -1;
+  }
+  return n;
 }
 
 // The debug taps in the order kdlae_t_forward passes them: per stage that runs, its input, then per

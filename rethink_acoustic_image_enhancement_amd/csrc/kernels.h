@@ -280,6 +280,18 @@ struct ConvLdsParams {
 bool conv_lds_supported(int kt, int ntiles, int cin_pad);
 hipError_t launch_conv_lds(const ConvLdsParams& p, hipStream_t s);
 
+// The sr head's cen (3x3, Cin -> hc) and upen (3x3, hc -> 2 hc, PixelShuffle(2)) as one 5x5 conv with 9
+// border-class weight sets (sr_fold.hip).  k-steps of 4 slots: 25 Cin taps + the bias slot, zero padded.
+constexpr int sr_fold_ksteps(int cin) { return (25 * cin + 1 + 3) / 4; }
+struct SrFoldParams {
+  const float* in; int Cin;        // hq, NCHW [Bn][Cin][H][W], Cin 1..4
+  const float* w; int ntiles;      // [9 classes][ntiles = 2 hc / 16][ksteps][64 lanes] (pack.hip, pack_fold_kernel)
+  float* out; int ldo;             // NHWC [Bn][2H][2W][ldo >= 4 ntiles], 16-byte aligned
+  int Bn, H, W;                    // H % 8 == 0, W % 8 == 0
+};
+bool sr_fold_supported(int cin, int ntiles);
+hipError_t launch_sr_fold(const SrFoldParams& p, hipStream_t s);
+
 // NIQE (niqe.hip): the block side at scale 1 (scale 2 uses half of it) and the 7 x 7 window of the MSCN filter,
 // handed to the kernel by value in the order scipy's convolve walks it (the caller's window reversed).
 constexpr int kNiqeBlock = 96;

@@ -4,6 +4,7 @@
 //   derive  BatchNorm scale / shift values (ASDQE), written after the parameters,
 //   gather  one packed float per thread: src[a] (x src[b], the LayerNorm weight folded into W),
 //   dot     folded biases: conv bias + W . (WithBias LayerNorm bias), accumulated in double,
+//   fold    the KDLAE-T sr head's cen and upen convs composed into 9 border-class 5x5 weight sets, in double,
 //   split   the GEMM weight blocks again in split fragment order (mfma3.h) into the split arena.
 // HBM-bound: per packed float 8 B of program + the gathered source floats + 4 B written.
 #include "runtime.h"
@@ -57,6 +58,48 @@ __global__ __launch_bounds__(256) void pack_dot_kernel(const PDot* __restrict__ 
   for (int k = 0; k < d.K; ++k)
     acc += (double)fetch(src, nsrc, ext, d.w + k) * (double)fetch(src, nsrc, ext, d.v + k);
   out[d.dst] = (float)acc;
+}
+
+// One float of the sr-head fold (runtime.h PFold, layout in kernels.h SrFoldParams): class cls = 3 rc + cc
+// (row / column class: 0 first, 1 interior, 2 last), output tile t, k-step s, lane (li, lq).  Row li of the
+// tile is pre-shuffle output n = 16 t + 4 (li & 3) + (li >> 2); slot k = 4 s + lq is tap (a, b) of input
+// channel c (k = 25 c + 5 a + b), then the bias slot, then zeros.
+//   W[n][c][a][b] = sum over the class's valid upen taps (dy, dx) with (a - dy, b - dx) a cen tap, and m,
+//                   of U[n][m][dy][dx] Cw[m][c][a - dy][b - dx]
+//   bias[n]       = sum over the class's valid upen taps and m of U[n][m][dy][dx] Cb[m]
+// A first-row pixel has no upen tap dy = 0 (it would read cen at row -1, which upen zero-pads), a last-row
+// pixel none with dy = 2; columns alike.  Summed in double in a fixed order, rounded once.
+__global__ __launch_bounds__(256) void pack_fold_kernel(PFold f, const float* __restrict__ src, float* __restrict__ out) {
+  const int ks = sr_fold_ksteps(f.cin), nt = f.ntiles(), K = 25 * f.cin;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= f.floats()) return;
+  const int lane = (int)(i & 63), li = lane & 15, lq = lane >> 4;
+  int64_t r = i >> 6;
+  const int s = (int)(r % ks);
+  r /= ks;
+  const int t = (int)(r % nt), cls = (int)(r / nt);
+  const int rc = cls / 3, cc = cls % 3;
+  const int n = 16 * t + 4 * (li & 3) + (li >> 2), k = 4 * s + lq;
+  const int dy0 = rc == 0 ? 1 : 0, dy1 = rc == 2 ? 1 : 2, dx0 = cc == 0 ? 1 : 0, dx1 = cc == 2 ? 1 : 2;
+  double acc = 0.0;
+  if (k < K) {
+    const int c = k / 25, a = (k % 25) / 5, b = k % 5;
+    for (int dy = dy0; dy <= dy1; ++dy)
+      for (int dx = dx0; dx <= dx1; ++dx) {
+        const int ey = a - dy, ex = b - dx;
+        if (ey < 0 || ey > 2 || ex < 0 || ex > 2) continue;
+        const float* u = src + f.U + ((int64_t)n * f.hc) * 9 + dy * 3 + dx;
+        const float* w = src + f.Cw + (int64_t)c * 9 + ey * 3 + ex;
+        for (int m = 0; m < f.hc; ++m) acc += (double)u[(int64_t)m * 9] * (double)w[(int64_t)m * f.cin * 9];
+      }
+  } else if (k == K && f.Cb >= 0) {
+    for (int dy = dy0; dy <= dy1; ++dy)
+      for (int dx = dx0; dx <= dx1; ++dx) {
+        const float* u = src + f.U + ((int64_t)n * f.hc) * 9 + dy * 3 + dx;
+        for (int m = 0; m < f.hc; ++m) acc += (double)u[(int64_t)m * 9] * (double)src[f.Cb + m];
+      }
+  }
+  out[f.dst + i] = (float)acc;
 }
 
 // one work item = (split record, lane): the lane's float4 of k-groups 2G and 2G + 1 -> 3 x 16 B
@@ -117,6 +160,7 @@ int DeviceWeights::upload_program(const PackProgram& p) {
   nsrc = p.nsrc;
   n_dots = (int)p.dots.size();
   n_der = (int)p.der.size();
+  fold = p.fold;
   std::vector<PEx> ex(p.ex);
   ex.resize(n);
   HIPCHK(hipMalloc(&dev, n * sizeof(float)));
@@ -158,6 +202,8 @@ int DeviceWeights::run(const float* params, hipStream_t s) const {
   if (n_dots)
     hipLaunchKernelGGL(pack_dot_kernel, dim3((n_dots + 255) / 256), dim3(256), 0, s, dots, n_dots, params, nsrc,
                        (const float*)ext, dev);
+  if (fold.dst >= 0)
+    hipLaunchKernelGGL(pack_fold_kernel, dim3((unsigned)((fold.floats() + 255) / 256)), dim3(256), 0, s, fold, params, dev);
   if (n_splits)
     hipLaunchKernelGGL(pack_split_kernel, dim3((unsigned)std::min<int64_t>((split_items + 255) / 256, 4096)), dim3(256),
                        0, s, splits, n_splits, split_items, (const float*)dev, dev3);
@@ -191,6 +237,7 @@ void DeviceWeights::release() {
   src = nullptr;
   n = 0;
   n_dots = n_der = 0;
+  fold = PFold{};
 }
 
 }  // namespace kdlae

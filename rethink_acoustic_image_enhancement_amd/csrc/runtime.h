@@ -81,10 +81,21 @@ struct PSplit {               // split arena [dst, +split3_floats) = split3 of t
   int64_t src = 0, dst = 0, first = 0;  // first: index of the descriptor's first work item (record x lane)
   int32_t ntiles = 0, kgroups = 0;
 };
+// Derived record: the KDLAE-T sr head's cen and upen convs composed into 9 border-class 5x5 weight sets
+// (sr_fold.hip reads them, pack_fold_kernel writes them after the gathers): arena [dst, dst + floats()).
+// U = upen.body.0.weight [2 hc][hc][3][3], Cw = cen.weight [hc][cin][3][3], Cb = cen.bias [hc] or -1.
+struct PFold {
+  int64_t dst = -1;           // < 0: the program has no fold
+  int32_t U = -1, Cw = -1, Cb = -1;
+  int32_t hc = 0, cin = 0;
+  constexpr int ntiles() const { return 2 * hc / 16; }
+  constexpr int64_t floats() const { return (int64_t)9 * ntiles() * sr_fold_ksteps(cin) * 64; }
+};
 struct PackProgram {
   std::vector<PEx> ex;        // one per arena float
   std::vector<PDot> dots;
   std::vector<PDer> der;
+  PFold fold;
   std::vector<PSplit> splits;  // run after the gathers and dots
   int64_t n3 = 0;              // floats in the split arena
   int64_t nsrc = 0;           // floats in the flat parameter vector
@@ -147,6 +158,7 @@ struct DeviceWeights {
   float* src = nullptr;       // flat parameters staged from the host (set_param/commit path)
   int64_t nsrc = 0;
   int n_dots = 0, n_der = 0;
+  PFold fold;
   int device = -1;
   int upload_program(const PackProgram& p);                 // allocates; synchronous, once per layout
   int run(const float* params, hipStream_t s) const;        // enqueues the pack on `s`
