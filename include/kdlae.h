@@ -165,6 +165,31 @@ int kdlae_t_forward_sr(kdlae_t_handle* h, const float* hq, int B, int H, int W, 
 int kdlae_rate_select(const float* scores, int R, int B, int mode, const float* target, const float* hq,
                       int64_t per_image, int32_t* index_out, float* hq_out, void* stream);
 
+/* Tiled inference: overlapping tiles of an image too large for one forward, blended on the device.
+ * The plan (fixed by H, W, tile, overlap; H % 8 == 0, W % 8 == 0, tile % 8 == 0, tile >= 16,
+ * 0 <= overlap < tile, anything else KDLAE_EINVAL_SHAPE):
+ *   th = min(tile, H), tw = min(tile, W)                       (per axis, not min(tile, H, W))
+ *   starts along an axis of length L with tile t: range(0, L - t, t - overlap) + [L - t], so tile i of n
+ *   starts at i stride for i < n - 1 and at L - t for the last; n = 1 when L == t (stride is then
+ *   reported as t and unused)
+ *   tile (b, i, j) has flat index (b ni + i) nj + j
+ * kdlae_tile_plan is host only and returns the plan.  kdlae_tile_gather copies tiles first .. first + count - 1
+ * of src [B][C][H][W] into dst [count][C][th][tw] (the image and, at C = 1, the rate map).  kdlae_tile_blend
+ * takes tiles [B ni nj][C][scale th][scale tw] (scale 1: hq, scale 2: sr, every coordinate doubled) and writes
+ * dst [B][C][scale H][scale W]: per pixel 0 + o1 + o2 + ... over the covering tiles in ascending flat index,
+ * in fp32, divided by the fp32 count of covering tiles; E.add_(patch), W.add_(1), E.div_(W) of the usual host
+ * loop, bit for bit (so a lone -0 comes out +0, as it does there).  One thread per output pixel group loops
+ * over its tiles: no atomics, the result is a function of the inputs alone.  Any float alignment of src, tiles
+ * and dst is accepted (16-byte accesses where pointers and starts allow, 4-byte otherwise).
+ * Null pointers, B, C, H, W or count < 1, first < 0, first + count > B ni nj, scale outside {1, 2}:
+ * KDLAE_EINVAL_CONFIG.  Every check comes before the launch. */
+int kdlae_tile_plan(int H, int W, int tile, int overlap, int* th, int* tw, int* ni, int* nj, int* stride_y,
+                    int* stride_x);
+int kdlae_tile_gather(const float* src, int B, int C, int H, int W, int tile, int overlap, int first, int count,
+                      float* dst, void* stream);
+int kdlae_tile_blend(const float* tiles, int B, int C, int H, int W, int tile, int overlap, int scale, float* dst,
+                     void* stream);
+
 /* Measurement hook for bench.py (no effect on results).  When a probe class is armed, every
  * launch of that kernel class inside kdlae_t_forward is bracketed by a pair of HIP events on
  * `stream`; kdlae_t_probe_read synchronises those events and returns the summed device time (ms),

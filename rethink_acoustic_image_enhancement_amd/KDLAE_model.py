@@ -325,7 +325,8 @@ class KDLAE_teacher(nn.Module):
     hip_graphs = True
     _GRAPH_CACHE = 4  # shapes kept per module (least recently used dropped)
 
-    def _forward_graphed(self, img, rate):
+    def _forward_graphed(self, img, rate, out=None):
+        """``out``: as in ``_forward_eager``; the replayed graph's outputs are copied there instead of cloned."""
         dev = img.device
         B, _, H, W = img.shape
         stream = torch.cuda.current_stream(dev)
@@ -344,7 +345,7 @@ class KDLAE_teacher(nn.Module):
                 if len(seen) > 64:
                     seen.clear()
                 seen.setdefault(key, 1)
-                return self._forward_eager(img, rate)
+                return self._forward_eager(img, rate, out=out)
             s_img = img.detach().to(torch.float32).contiguous().clone()
             s_rate = rate.detach().to(device=dev, dtype=torch.float32).contiguous().clone() if rate is not None else None
             g = torch.cuda.CUDAGraph()
@@ -357,7 +358,7 @@ class KDLAE_teacher(nn.Module):
             except RuntimeError:
                 seen[key] = 2  # this shape stays eager
                 torch.cuda.synchronize(dev)
-                return self._forward_eager(img, rate)
+                return self._forward_eager(img, rate, out=out)
             ent = (g, s_img, s_rate, s_out, (eng.ws.data_ptr(), eng.flat.data_ptr()))
             while len(cache) >= self._GRAPH_CACHE:
                 cache.pop(next(iter(cache)))
@@ -367,10 +368,17 @@ class KDLAE_teacher(nn.Module):
         if s_rate is not None:
             s_rate.copy_(rate.detach())
         g.replay()
+        if out is not None:
+            for dst, k in zip(out, ("hq", "sr")):
+                if dst is not None:
+                    dst.copy_(s_out[k])
+            return {"hq": out[0], "sr": out[1]}
         return {k: (v.clone() if v is not None else None) for k, v in s_out.items()}
 
-    def _forward_eager(self, img, rate, flat=None):
-        """``flat``: run with this packed parameter vector (``_Engine.pack_flat``) instead of the module's own."""
+    def _forward_eager(self, img, rate, flat=None, out=None):
+        """``flat``: run with this packed parameter vector (``_Engine.pack_flat``) instead of the module's own.
+        ``out``: ``(hq, sr)`` contiguous fp32 destinations of the outputs' shapes (``sr`` None without the sr
+        head) to write into instead of fresh tensors: how ``forward_tiled`` fills its staging."""
         dev = img.device
         B, _, H, W = img.shape
         cat = rate is not None
@@ -384,8 +392,12 @@ class KDLAE_teacher(nn.Module):
         img_c = img.detach().to(torch.float32).contiguous()
         rate_c = denoise_rate.detach().to(device=dev, dtype=torch.float32).contiguous() if cat else None
         oc = self._cfg["out_channels"]
-        hq = torch.empty((B, oc, H, W), device=dev, dtype=torch.float32)
-        sr = torch.empty((B, oc, 2 * H, 2 * W), device=dev, dtype=torch.float32) if self.static == "train" else None
+        if out is not None:
+            hq, sr = out
+        else:
+            hq = torch.empty((B, oc, H, W), device=dev, dtype=torch.float32)
+            sr = torch.empty((B, oc, 2 * H, 2 * W), device=dev, dtype=torch.float32) if self.static == "train" \
+                else None
         L = _lib.lib()
         nbytes = L.kdlae_t_workspace_bytes(eng.handle, B, H, W)
         if nbytes < 0:
@@ -396,6 +408,60 @@ class KDLAE_teacher(nn.Module):
                                ctypes.c_void_p(hq.data_ptr()), ctypes.c_void_p(sr.data_ptr() if sr is not None else 0),
                                ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.c_void_p(stream))
         _lib.check(rc, "kdlae_t_forward")
+        return {"hq": hq, "sr": sr}
+
+    # ------------------------------------------------------------------ tiled inference
+    def forward_tiled(self, input, tile=512, tile_overlap=32, tile_batch=16):
+        """``forward`` for images larger than one forward can hold: overlapping ``tile`` x ``tile`` tiles (clamped
+        per axis to the image), ``tile_overlap`` pixels shared by neighbours, every covered pixel the plain mean of
+        its tiles' outputs (tiling.py and include/kdlae.h state the plan and the sum order; it is upstream
+        Restormer's ``--tile`` / ``--tile_overlap`` rule).  Tiles are gathered on the device ``tile_batch`` at a
+        time and go through this module's own inference forward, so every full chunk replays one HIP graph; the
+        outputs land in a staging tensor and one blend launch per output writes the result.
+
+        Returns ``{"hq": [B,C,H,W], "sr": [B,C,2H,2W] or None}``.  Each tile's rows are bit for bit what ``forward``
+        gives for that tile alone, for every ``tile_batch``; with one tile per image the result equals ``forward``.
+        MDTA's channel attention is global over the pixels it is given, so with more than one tile the result is a
+        different function of the image from the untiled ``forward`` (as upstream), not an approximation of it
+        that carries a bound.  Inference only (eval mode, no autograd graph)."""
+        self._check_inference_input(input["img"], "forward_tiled")
+        with torch.no_grad():
+            return self._forward_tiled(input["img"], input.get("denoise_rate"), tile, tile_overlap, tile_batch)
+
+    def _forward_tiled(self, img, rate, tile, tile_overlap, tile_batch, flat=None):
+        """``flat``: as in ``_forward_eager`` (a trainer's flat parameters; always launched one by one)."""
+        from . import tiling
+        ci, oc = self._cfg["inp_channels"], self._cfg["out_channels"]
+        if img.dim() != 4 or img.shape[1] != ci:
+            raise RuntimeError(f"expected img [B,{ci},H,W], got {tuple(img.shape)}")
+        B, _, H, W = img.shape
+        if int(tile_batch) < 1:
+            raise RuntimeError(f"tile_batch must be at least 1, got {tile_batch}")
+        plan = tiling.tile_plan(H, W, tile, tile_overlap)   # refuses a bad shape / tile / overlap before any launch
+        cat = self._cfg["params"] == "cat"
+        if cat and (rate is None or tuple(rate.shape) != (B, 1, H, W)):
+            raise RuntimeError(f"denoise_rate must be [B,1,H,W]={B, 1, H, W}, got "
+                               f"{tuple(rate.shape) if rate is not None else None}")
+        dev = img.device
+        img_c = img.detach().to(torch.float32).contiguous()
+        rate_c = rate.detach().to(device=dev, dtype=torch.float32).contiguous() if cat else None
+        n = B * plan.ni * plan.nj
+        th, tw = plan.th, plan.tw
+        has_sr = self.static == "train"
+        st_hq = torch.empty((n, oc, th, tw), device=dev, dtype=torch.float32)
+        st_sr = torch.empty((n, oc, 2 * th, 2 * tw), device=dev, dtype=torch.float32) if has_sr else None
+        graphed = flat is None and self.hip_graphs and not torch.cuda.is_current_stream_capturing()
+        for first in range(0, n, int(tile_batch)):
+            count = min(int(tile_batch), n - first)
+            t_img = tiling.tile_gather(img_c, tile, tile_overlap, first, count)
+            t_rate = tiling.tile_gather(rate_c, tile, tile_overlap, first, count) if cat else None
+            out = (st_hq[first:first + count], st_sr[first:first + count] if has_sr else None)
+            if graphed:
+                self._forward_graphed(t_img, t_rate, out=out)
+            else:
+                self._forward_eager(t_img, t_rate, flat=flat, out=out)
+        hq = tiling.tile_blend(st_hq, B, H, W, tile, tile_overlap, 1)
+        sr = tiling.tile_blend(st_sr, B, H, W, tile, tile_overlap, 2) if has_sr else None
         return {"hq": hq, "sr": sr}
 
     # ------------------------------------------------------------------ rate sweep

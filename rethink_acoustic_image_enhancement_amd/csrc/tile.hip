@@ -1,0 +1,202 @@
+// Tiled inference (kdlae_tile_plan, kdlae_tile_gather, kdlae_tile_blend): both kernels move bytes, the blend
+// also adds and divides.
+//
+//   plan                per axis of length L: t = min(tile, L), stride = t - overlap, starts
+//                       range(0, L - t, stride) + [L - t], so n = ceil((L - t) / stride) + 1 (1 when L == t) and
+//                       start(i) = i < n - 1 ? i stride : L - t.  No start table: both kernels derive the start.
+//   tile_gather_kernel  tiles first .. first + count - 1 (flat index (b ni + i) nj + j) of src [B][C][H][W] ->
+//                       dense [count][C][th][tw].  One item per V consecutive floats of a destination row.
+//   tile_blend_kernel   gather form: one thread per V consecutive output pixels loops over the covering tiles in
+//                       ascending flat index (i outer, j inner), acc = 0 + o1 + o2 + ... in fp32, then divides by
+//                       the fp32 count: E.add_(patch); W.add_(1); E.div_(W) of the host loop, bit for bit.
+//                       No atomics.  scale 2 (the sr output) is the same plan with every coordinate doubled.
+//
+// V = 4 (float4 loads and stores) when both base pointers sit on 16 bytes and every tile start along x is a
+// multiple of 4 floats (H, W and tile are multiples of 8, so that is a condition on the stride alone); V = 1
+// otherwise (odd overlaps, offset storage).  In the V = 4 blend all tile edges are multiples of 4, so the four
+// pixels of a thread share one cover set.  Flat 64-bit item index with a grid-stride loop: no image is too wide
+// or too tall for the grid.
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cstdint>
+
+#include "runtime.h"
+
+namespace kdlae {
+
+struct TilePlan {
+  int th = 0, tw = 0, ni = 0, nj = 0, sy = 0, sx = 0;
+};
+
+// kernel geometry, already multiplied by the blend's scale: L = image, t = tile, s = stride, n = tiles
+struct TileGeo {
+  int Ly, Lx, ty, tx, sy, sx, ni, nj;
+};
+
+constexpr long long kTileMaxBlocks = 4096;  // 16 blocks of 256 per CU; the loop takes the rest
+
+__device__ __forceinline__ int tile_start(int i, int n, int stride, int last) { return i < n - 1 ? i * stride : last; }
+
+template <int V>
+__global__ __launch_bounds__(256) void tile_gather_kernel(const float* __restrict__ src, float* __restrict__ dst,
+                                                          TileGeo g, int C, int first, long long total) {
+  const int twq = g.tx / V;
+  for (long long idx = blockIdx.x * 256LL + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
+    const long long row = idx / twq;  // over count C th
+    const int x = (int)(idx - row * twq) * V;
+    const int y = (int)(row % g.ty);
+    const long long kc = row / g.ty;
+    const int c = (int)(kc % C);
+    const int flat = first + (int)(kc / C);
+    const int j = flat % g.nj, bi = flat / g.nj;
+    const int i = bi % g.ni, b = bi / g.ni;
+    const int y0 = tile_start(i, g.ni, g.sy, g.Ly - g.ty), x0 = tile_start(j, g.nj, g.sx, g.Lx - g.tx);
+    const float* __restrict__ s = src + (((long long)b * C + c) * g.Ly + y0 + y) * g.Lx + x0 + x;
+    if constexpr (V == 4)
+      reinterpret_cast<float4*>(dst)[idx] = *reinterpret_cast<const float4*>(s);
+    else
+      dst[idx] = *s;
+  }
+}
+
+// tiles covering coordinate p along one axis: the regular ones lo .. hi (start i s, i < n - 1) and, with `last`,
+// tile n - 1 at L - t; ascending index is ascending start
+struct Cover {
+  int lo, hi, last;
+};
+__device__ __forceinline__ Cover tile_cover(int p, int L, int t, int s, int n) {
+  Cover c;
+  c.lo = p >= t ? (p - t) / s + 1 : 0;
+  c.hi = min(p / s, n - 2);
+  c.last = p >= L - t;
+  return c;
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void tile_blend_kernel(const float* __restrict__ tiles, float* __restrict__ dst,
+                                                         TileGeo g, int C, long long total) {
+  const int wq = g.Lx / V;
+  for (long long idx = blockIdx.x * 256LL + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
+    const long long row = idx / wq;  // over B C Ly
+    const int X = (int)(idx - row * wq) * V;
+    const int Y = (int)(row % g.Ly);
+    const long long bc = row / g.Ly;
+    const int c = (int)(bc % C), b = (int)(bc / C);
+    const Cover cy = tile_cover(Y, g.Ly, g.ty, g.sy, g.ni), cx = tile_cover(X, g.Lx, g.tx, g.sx, g.nj);
+    float acc[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) acc[e] = 0.f;
+    int cnt = 0;
+    for (int ii = cy.lo; ii <= cy.hi + cy.last; ++ii) {
+      const int i = ii <= cy.hi ? ii : g.ni - 1;
+      const int yt = Y - (ii <= cy.hi ? i * g.sy : g.Ly - g.ty);
+      for (int jj = cx.lo; jj <= cx.hi + cx.last; ++jj) {
+        const int j = jj <= cx.hi ? jj : g.nj - 1;
+        const int xt = X - (jj <= cx.hi ? j * g.sx : g.Lx - g.tx);
+        const long long flat = ((long long)b * g.ni + i) * g.nj + j;
+        const float* __restrict__ t = tiles + ((flat * C + c) * g.ty + yt) * g.tx + xt;
+        if constexpr (V == 4) {
+          const float4 v = *reinterpret_cast<const float4*>(t);
+          acc[0] += v.x;
+          acc[1] += v.y;
+          acc[2] += v.z;
+          acc[3] += v.w;
+        } else {
+          acc[0] += *t;
+        }
+        ++cnt;
+      }
+    }
+    const float w = (float)cnt;
+    if constexpr (V == 4)
+      reinterpret_cast<float4*>(dst)[idx] = make_float4(acc[0] / w, acc[1] / w, acc[2] / w, acc[3] / w);
+    else
+      dst[idx] = acc[0] / w;
+  }
+}
+
+static int axis_tiles(int L, int t, int stride) { return L == t ? 1 : (int)ceil_div(L - t, stride) + 1; }
+
+// the argument checks every entry shares; `who` names the entry in the message
+static int make_plan(const char* who, int H, int W, int tile, int overlap, TilePlan& p) {
+  const std::string w(who);
+  if (H < 1 || W < 1) return fail(KDLAE_EINVAL_CONFIG, w + ": H and W must be positive");
+  if (H % 8 || W % 8) return fail(KDLAE_EINVAL_SHAPE, w + ": need H % 8 == 0 and W % 8 == 0");
+  if (tile < 16 || tile % 8) return fail(KDLAE_EINVAL_SHAPE, w + ": tile must be a multiple of 8, at least 16");
+  if (overlap < 0 || overlap >= tile) return fail(KDLAE_EINVAL_SHAPE, w + ": need 0 <= overlap < tile");
+  p.th = std::min(tile, H);
+  p.tw = std::min(tile, W);
+  // an axis the tile covers whole has one tile and no stride to speak of: report the tile size
+  p.sy = H > p.th ? p.th - overlap : p.th;
+  p.sx = W > p.tw ? p.tw - overlap : p.tw;
+  p.ni = axis_tiles(H, p.th, p.sy);
+  p.nj = axis_tiles(W, p.tw, p.sx);
+  return KDLAE_OK;
+}
+
+static unsigned tile_blocks(long long total) { return (unsigned)std::min(ceil_div(total, 256), kTileMaxBlocks); }
+
+}  // namespace kdlae
+
+using namespace kdlae;
+
+extern "C" int kdlae_tile_plan(int H, int W, int tile, int overlap, int* th, int* tw, int* ni, int* nj,
+                               int* stride_y, int* stride_x) {
+  if (!th || !tw || !ni || !nj || !stride_y || !stride_x)
+    return fail(KDLAE_EINVAL_CONFIG, "kdlae_tile_plan: null argument");
+  TilePlan p;
+  TRY(make_plan("kdlae_tile_plan", H, W, tile, overlap, p));
+  *th = p.th, *tw = p.tw, *ni = p.ni, *nj = p.nj, *stride_y = p.sy, *stride_x = p.sx;
+  return KDLAE_OK;
+}
+
+extern "C" int kdlae_tile_gather(const float* src, int B, int C, int H, int W, int tile, int overlap, int first,
+                                 int count, float* dst, void* stream) {
+  if (!src || !dst) return fail(KDLAE_EINVAL_CONFIG, "kdlae_tile_gather: null argument");
+  if (B < 1 || C < 1 || count < 1 || first < 0)
+    return fail(KDLAE_EINVAL_CONFIG, "kdlae_tile_gather: need B, C, count >= 1 and first >= 0");
+  TilePlan p;
+  TRY(make_plan("kdlae_tile_gather", H, W, tile, overlap, p));
+  const long long ntiles = (long long)B * p.ni * p.nj;
+  if (ntiles > INT_MAX) return fail(KDLAE_EINVAL_SHAPE, "kdlae_tile_gather: more than 2^31 - 1 tiles");
+  if ((long long)first + count > ntiles)
+    return fail(KDLAE_EINVAL_CONFIG, "kdlae_tile_gather: first + count passes the last tile (B ni nj = " +
+                                         std::to_string(ntiles) + ")");
+  const TileGeo g{H, W, p.th, p.tw, p.sy, p.sx, p.ni, p.nj};
+  const long long floats = (long long)count * C * p.th * p.tw;
+  const bool vec = al16(src) && al16(dst) && (p.nj == 1 || p.sx % 4 == 0);
+  if (vec)
+    hipLaunchKernelGGL(tile_gather_kernel<4>, dim3(tile_blocks(floats / 4)), dim3(256), 0, (hipStream_t)stream, src,
+                       dst, g, C, first, floats / 4);
+  else
+    hipLaunchKernelGGL(tile_gather_kernel<1>, dim3(tile_blocks(floats)), dim3(256), 0, (hipStream_t)stream, src, dst,
+                       g, C, first, floats);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(KDLAE_EHIP, hipGetErrorString(e));
+  return KDLAE_OK;
+}
+
+extern "C" int kdlae_tile_blend(const float* tiles, int B, int C, int H, int W, int tile, int overlap, int scale,
+                                float* dst, void* stream) {
+  if (!tiles || !dst) return fail(KDLAE_EINVAL_CONFIG, "kdlae_tile_blend: null argument");
+  if (B < 1 || C < 1) return fail(KDLAE_EINVAL_CONFIG, "kdlae_tile_blend: need B >= 1 and C >= 1");
+  if (scale != 1 && scale != 2) return fail(KDLAE_EINVAL_CONFIG, "kdlae_tile_blend: scale must be 1 or 2");
+  TilePlan p;
+  TRY(make_plan("kdlae_tile_blend", H, W, tile, overlap, p));
+  if ((long long)B * p.ni * p.nj > INT_MAX || (long long)scale * std::max(H, W) > INT_MAX)
+    return fail(KDLAE_EINVAL_SHAPE, "kdlae_tile_blend: more than 2^31 - 1 tiles or pixels along an axis");
+  const int s = scale;
+  const TileGeo g{s * H, s * W, s * p.th, s * p.tw, s * p.sy, s * p.sx, p.ni, p.nj};
+  const long long floats = (long long)B * C * g.Ly * g.Lx;
+  const bool vec = al16(tiles) && al16(dst) && (p.nj == 1 || g.sx % 4 == 0);
+  if (vec)
+    hipLaunchKernelGGL(tile_blend_kernel<4>, dim3(tile_blocks(floats / 4)), dim3(256), 0, (hipStream_t)stream, tiles,
+                       dst, g, C, floats / 4);
+  else
+    hipLaunchKernelGGL(tile_blend_kernel<1>, dim3(tile_blocks(floats)), dim3(256), 0, (hipStream_t)stream, tiles, dst,
+                       g, C, floats);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(KDLAE_EHIP, hipGetErrorString(e));
+  return KDLAE_OK;
+}

@@ -5,6 +5,8 @@
   multiple of 8, constant ``denoise_rate`` map, forward, then clamp / crop / ``img_as_ubyte`` and the
   zero-mask of input-black pixels (x2 nearest for ``sr``).  Pre and post are HIP kernels
   (``kdlae_preprocess_u8`` / ``kdlae_postprocess_u8``); images never round-trip through the host.
+* ``enhance_tiled_u8`` — the same cell for images too large for one forward: ``KDLAE_teacher.forward_tiled``
+  between the same pre and post kernels (tiling.py).
 * ``enhance_rates_u8`` / ``enhance_auto_u8`` — the notebook's "pick a rate, look, pick again" loop as one
   call: R rates of the same images through ``KDLAE_teacher.forward_rates`` (the rate-independent trunk runs
   once), every candidate post-processed as the notebook saves it, and — ``enhance_auto_u8`` — scored by
@@ -77,6 +79,21 @@ def enhance_u8(model, images: torch.Tensor, denoise_rate, bgr: bool = False, mul
     img, rmap = preprocess_u8(images, denoise_rate, multiple, bgr)
     with torch.no_grad():
         pred = model({"img": img, "denoise_rate": rmap})
+    hq = postprocess_u8(pred["hq"], h, w, 1, images)
+    sr = postprocess_u8(pred["sr"], h, w, 2, images) if pred.get("sr") is not None else None
+    return hq, sr
+
+
+def enhance_tiled_u8(model, images: torch.Tensor, denoise_rate, tile: int = 512, tile_overlap: int = 32,
+                     tile_batch: int = 16, bgr: bool = False, multiple: int = 8):
+    """``enhance_u8`` for images larger than one forward can hold: the same pre- and post-processing around
+    ``KDLAE_teacher.forward_tiled`` (overlapping tiles blended on the device) -> (hq u8, sr u8 or None).  A tiled
+    result is a different function of the image from ``enhance_u8``'s (MDTA's channel attention is global over
+    the pixels of each tile), as it is in upstream Restormer's tiled demo; it equals it when one tile covers
+    the padded image."""
+    B, h, w, C = images.shape
+    img, rmap = preprocess_u8(images, denoise_rate, multiple, bgr)
+    pred = model.forward_tiled({"img": img, "denoise_rate": rmap}, tile, tile_overlap, tile_batch)
     hq = postprocess_u8(pred["hq"], h, w, 1, images)
     sr = postprocess_u8(pred["sr"], h, w, 2, images) if pred.get("sr") is not None else None
     return hq, sr

@@ -1,0 +1,98 @@
+"""Tiled inference: overlapping tiles of an image too large for one forward, blended on the device.
+
+Thin wrappers of ``kdlae_tile_plan`` / ``kdlae_tile_gather`` / ``kdlae_tile_blend`` (include/kdlae.h states the
+semantics) on the current stream.  ``KDLAE_teacher.forward_tiled`` and ``pipeline.enhance_tiled_u8`` are built
+on them.  The plan follows upstream Restormer's demo (``--tile`` / ``--tile_overlap``): starts
+``range(0, L - t, t - tile_overlap) + [L - t]`` per axis, a plain sum over the covering tiles in tile order and
+a division by their count; the tile is clamped per axis (``th = min(tile, H)``, ``tw = min(tile, W)``).
+
+MDTA's channel attention is global over the pixels of whatever it is given, so a tile's output depends on the
+tile alone and a tiled result is a different function of the image from the untiled forward, exactly as it is
+upstream: it is not an approximation of the untiled result that carries an error bound."""
+from __future__ import annotations
+
+import ctypes
+from typing import NamedTuple
+
+import torch
+
+from . import _lib
+
+
+class TilePlan(NamedTuple):
+    th: int
+    tw: int
+    ni: int
+    nj: int
+    stride_y: int
+    stride_x: int
+
+    def starts(self, H: int, W: int):
+        """Tile starts along y and x."""
+        return ([i * self.stride_y for i in range(self.ni - 1)] + [H - self.th],
+                [j * self.stride_x for j in range(self.nj - 1)] + [W - self.tw])
+
+
+def _stream(dev):
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def tile_plan(H: int, W: int, tile: int = 512, tile_overlap: int = 32) -> TilePlan:
+    """``kdlae_tile_plan``: host only.  RuntimeError unless H % 8 == W % 8 == tile % 8 == 0, tile >= 16 and
+    0 <= tile_overlap < tile."""
+    out = [ctypes.c_int() for _ in range(6)]
+    rc = _lib.lib().kdlae_tile_plan(int(H), int(W), int(tile), int(tile_overlap), *[ctypes.byref(v) for v in out])
+    _lib.check(rc, "kdlae_tile_plan")
+    return TilePlan(*[v.value for v in out])
+
+
+def _check_f32_cuda(t: torch.Tensor, what: str):
+    if t.device.type != "cuda" or t.dtype != torch.float32 or t.dim() != 4:
+        raise RuntimeError(f"{what} expects a cuda float32 tensor with 4 dimensions, got {t.dtype} "
+                           f"{tuple(t.shape)} on {t.device}")
+
+
+def tile_gather(src: torch.Tensor, tile: int = 512, tile_overlap: int = 32, first: int = 0, count: int | None = None,
+                out: torch.Tensor | None = None) -> torch.Tensor:
+    """Tiles ``first .. first + count - 1`` (flat index ``(b ni + i) nj + j``; default: all of them) of
+    ``src`` [B,C,H,W] -> dense [count,C,th,tw].  ``out``: a contiguous destination of that shape."""
+    _check_f32_cuda(src, "tile_gather")
+    src = src.contiguous()
+    B, C, H, W = src.shape
+    p = tile_plan(H, W, tile, tile_overlap)
+    if count is None:
+        count = B * p.ni * p.nj - first
+    shape = (count, C, p.th, p.tw)
+    if out is None:
+        out = torch.empty(shape, device=src.device, dtype=torch.float32)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != src.device or \
+            not out.is_contiguous():
+        raise RuntimeError(f"tile_gather: out must be a contiguous float32 {shape} on {src.device}")
+    rc = _lib.lib().kdlae_tile_gather(ctypes.c_void_p(src.data_ptr()), B, C, H, W, int(tile), int(tile_overlap),
+                                      int(first), int(count), ctypes.c_void_p(out.data_ptr()), _stream(src.device))
+    _lib.check(rc, "kdlae_tile_gather")
+    return out
+
+
+def tile_blend(tiles: torch.Tensor, B: int, H: int, W: int, tile: int = 512, tile_overlap: int = 32, scale: int = 1,
+               out: torch.Tensor | None = None) -> torch.Tensor:
+    """``tiles`` [B ni nj, C, scale th, scale tw] of a [B,C,H,W] image's plan -> [B, C, scale H, scale W]: per
+    pixel the fp32 sum of the covering tiles in flat-index order over their fp32 count."""
+    _check_f32_cuda(tiles, "tile_blend")
+    tiles = tiles.contiguous()
+    p = tile_plan(H, W, tile, tile_overlap)
+    C = tiles.shape[1]
+    want = (B * p.ni * p.nj, C, scale * p.th, scale * p.tw)
+    if scale in (1, 2) and tuple(tiles.shape) != want:
+        raise RuntimeError(f"tile_blend: expected tiles {want}, got {tuple(tiles.shape)}")
+    shape = (B, C, scale * H, scale * W)
+    if out is None:
+        out = torch.empty(shape, device=tiles.device, dtype=torch.float32)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != tiles.device or \
+            not out.is_contiguous():
+        raise RuntimeError(f"tile_blend: out must be a contiguous float32 {shape} on {tiles.device}")
+    rc = _lib.lib().kdlae_tile_blend(ctypes.c_void_p(tiles.data_ptr()), int(B), C, int(H), int(W), int(tile),
+                                     int(tile_overlap), int(scale), ctypes.c_void_p(out.data_ptr()),
+                                     _stream(tiles.device))
+    _lib.check(rc, "kdlae_tile_blend")
+    return out

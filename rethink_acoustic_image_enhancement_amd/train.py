@@ -1193,7 +1193,7 @@ class KDLAETrainer(_TrainingState):
 
     @torch.no_grad()
     def validate(self, batches, window_size=8, crop_border=0, use_image=False, use_ema=None, metrics=("psnr",),
-                 niqe=False, niqe_params=None):
+                 niqe=False, niqe_params=None, tile=None, tile_overlap=32, tile_batch=16):
         """ImageCleanModel.nondist_validation with pad_test (image_restoration_model.py:226-348) over
         ``(lq, gt)`` pairs, ``lq = {'img', 'denoise_rate'}``, ``gt = {'hq', 'sr'}``: reflect-pad ``img`` and the
         rate map right and bottom to a multiple of ``window_size``, run the inference engine
@@ -1205,6 +1205,12 @@ class KDLAETrainer(_TrainingState):
         val.metrics type, no target needed) of the outputs' windows, always on ``tensor2img``'s uint8 image,
         which is what the reference's function takes (at least 96 x 96 pixels after ``crop_border``);
         ``niqe_params`` is the reference's pristine model (``metrics.load_niqe_params``).
+
+        ``tile``: validate images too large for one forward.  The padded image goes through the tiled forward
+        (``KDLAE_teacher.forward_tiled``'s tiles, ``tile_overlap`` and ``tile_batch``, with the weights chosen
+        below) instead of one ``kdlae_t_forward``; the padded sizes must then be multiples of 8.  A tiled output
+        is a different function of the image from the untiled one (MDTA's attention is global over each tile),
+        so its metrics are not comparable digit for digit with ``tile=None``, today's path.
 
         ``use_ema=None``: the EMA weights when ``ema_decay > 0`` (net_g_ema, :242-248), else the live ones.
         The chosen flat vector is packed straight into the module's inference handle; the trainer's buffers,
@@ -1227,7 +1233,10 @@ class KDLAETrainer(_TrainingState):
             img_p = _reflect_pad(img.to(torch.float32), window_size)
             rate_p = _reflect_pad(rate.to(device=img.device, dtype=torch.float32), window_size) if rate is not None \
                 else None
-            out = self.model._forward_eager(img_p, rate_p, flat=flat)
+            if tile is None:
+                out = self.model._forward_eager(img_p, rate_p, flat=flat)
+            else:
+                out = self.model._forward_tiled(img_p, rate_p, tile, tile_overlap, tile_batch, flat=flat)
             # the last item's cropped outputs (pad_test's self.output, :236-237), as views
             self.val_output = {"hq": out["hq"][..., :h, :w],
                                "sr": out["sr"][..., :2 * h, :2 * w] if out["sr"] is not None else None}
