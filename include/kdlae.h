@@ -117,7 +117,24 @@ int kdlae_t_pack_device(kdlae_t_handle* h, const float* params, int64_t numel, v
 int kdlae_t_set_param(kdlae_t_handle* h, const char* name, const float* host_data, int64_t numel);
 int kdlae_t_commit_params(kdlae_t_handle* h, void* stream);
 
-/* Device bytes of caller-owned scratch needed by kdlae_t_forward for a B x H x W batch. */
+/* Workspace contract, for every *_workspace_bytes query and every entry point that takes a `workspace` in this
+ * header (kdlae_t_forward / _forward_rates / _forward_sr, kdlae_s_forward, asdqe_forward, kdlae_tt_*, kdlae_st_*,
+ * asdqe_train_*):
+ *   - the query's answer is positive (-1 with kdlae_last_error for arguments the entry point would refuse) and a
+ *     multiple of 256; `workspace` must be 256-byte aligned (every buffer the plan carves out of it then is);
+ *   - the contents of the workspace on entry are arbitrary: it needs no initialisation, may be reused across
+ *     shapes, calls and handles, and may hold anything (another call's leftovers, NaNs); whatever a call reads
+ *     from it, that call (or, for a backward, its forward) wrote first, so no output depends on them;
+ *   - the output buffers' contents on entry are arbitrary too: outputs are overwritten (`grad` as well, unless
+ *     an `accumulate` argument says otherwise);
+ *   - workspace_bytes below the query's answer is refused with KDLAE_ESTATE ("... workspace too small") before
+ *     anything is launched; with the answer itself the call writes nothing outside [workspace, workspace + bytes)
+ *     and its outputs, and never writes a read-only operand;
+ *   - a training forward leaves its activations in the workspace: the same pointer, with its contents unchanged,
+ *     must reach the matching backward.
+ * tests/test_workspace_gpu.py holds every entry point to this with guarded, poisoned workspaces.
+ *
+ * Device bytes of caller-owned scratch needed by kdlae_t_forward for a B x H x W batch. */
 int64_t kdlae_t_workspace_bytes(const kdlae_t_handle* h, int B, int H, int W);
 
 /* replaces KDLAE_teacher.forward (KDLAE_model.py:270-336):

@@ -1164,7 +1164,7 @@ int64_t kdlae_tt_workspace_bytes(kdlae_tt_handle* h, int B, int H, int W) {
   h->ws_B = B;
   h->ws_H = H;
   h->ws_W = W;
-  h->ws_bytes = (int64_t)c.peak;
+  h->ws_bytes = (int64_t)((c.peak + 255) / 256 * 256);  // a multiple of 256, as every workspace query's answer
   return h->ws_bytes;
 }
 
