@@ -23,7 +23,11 @@
  * the same bits: "no_attn_in_fusion" keeps the attention-output GEMM and the
  * LN + ffn.project_in GEMM separate (every block); "no_attn_in_split" keeps
  * them separate for the C = 96 blocks only (by default their first
- * project_in weight group is fused as well).  One flag selects between two
+ * project_in weight group is fused as well); "no_attn_out_dw" keeps the
+ * v-writing Gram ring and the per-image attention-output GEMM on the C = 48 /
+ * 96 blocks; "gdfn_split" runs the C = 192 / 384 GDFN tails as C / 96 blocks
+ * per pixel tile (gdfn_out_kernel<6, 8>) instead of gdfn_once_kernel, which
+ * stages and gates a pixel tile once per 192 output channels.  One flag selects between two
  * evaluation orders that agree to fp32 rounding, not to the bit: "no_sr_fold"
  * keeps the sr head's cen and upen convs as two launches instead of the one
  * composed 5x5 conv (csrc/sr_fold.hip).  KDLAE_PROBE_DUMP
@@ -901,7 +905,8 @@ int kdlae_debug_train_s(const kdlae_debug_train_s_desc* d, void* stream);
  * channel c at 32 t + 16 h + c, bias at 288 + 16 h + c (gdfn.hip).
  *   op 0 gdfn_out       in0 = project_in rows [P][2 hidS] chunk-interleaved (ldi0 == 2 hidS), w0 = dw blocks,
  *                       w1 = project_out [C/16][hidS/16] fragments, bias0 [C] (or null), R / ldr (or null; may be
- *                       out0), zeros (>= 16 zero floats) -> out0 (C)
+ *                       out0), zeros (>= 16 zero floats) -> out0 (C); out_mode 0 = the default launches, 1 = C = 192 /
+ *                       384 as C / 96 blocks per pixel tile (what KDLAE_DEBUG=gdfn_split selects; the same bits)
  *   op 1 ffn_fused      in0 = x (C), ln, w0 = project_in [2 hidS/16][C/16] fragments (chunk-interleaved rows),
  *                       bias0 [2 hidS] (chunk-interleaved, or null), w1 = dw blocks, w2 = project_out fragments,
  *                       bias1 [C] (or null) -> out0 = x + ffn(LN(x)) (must not overlap in0)

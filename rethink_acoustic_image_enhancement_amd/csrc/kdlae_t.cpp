@@ -32,6 +32,9 @@ struct BlockW {
   size_t dwqkv = kNone, dwqkv_b = kNone, proj = kNone, proj_b = kNone, temp = kNone;
   size_t dwffn = kNone, dwffn_b = kNone;
   bool fused_gdfn = false;  // project_in output chunk-interleaved; dwconv+gate+project_out in one kernel
+  // debug flag gdfn_split: the C = 192 / 384 tails as C / 96 blocks per pixel tile (gdfn_out_kernel<6, 8>)
+  // instead of gdfn_once_kernel (A/B baseline and bit-identity reference)
+  bool gdfn_split = false;
   bool fused_attn_in = false;  // x1 = x + M v, LN and project_in in one GEMM kernel (gemm_attn_in_kernel)
   // when project_in needs two resident weight groups (C = 96): the fused kernel runs group 0 (and
   // forms x1), a plain LN GEMM on x1 runs group 1
@@ -361,6 +364,7 @@ struct Packer {
     // (C96@512^2 3.54 vs 3.41 ms, C48@1024^2 5.93 vs 5.29 ms; DESIGN.md §4 "Fused MDTA pass 1")
     b.mdta_fused = heads == 1 && (C == 48 || C == 96) && b.qkv.ntiles == 3 * C / 16 && debug_flag("mdta_fusion");
     b.attn_out_dw = (C == 48 || C == 96) && b.Ch <= 96 && !debug_flag("no_attn_out_dw");
+    b.gdfn_split = debug_flag("gdfn_split");
     return b;
   }
 
@@ -722,6 +726,7 @@ struct Fwd {
       gd.H = Hh;
       gd.W = Ww;
       gd.zeros = h->P(h->zeros);
+      gd.split = b.gdfn_split;
       if ((rc = probe_begin(3, b.C))) return rc;
       tag = "gdfn C" + std::to_string(b.C) + " hid" + std::to_string(b.hid) + " HW" + std::to_string(HW);
       HIPCHK(launch_gdfn_out(gd, b.C, s));

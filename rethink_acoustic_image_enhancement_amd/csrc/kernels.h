@@ -148,6 +148,8 @@ struct GdfnParams {
   int Bn, H, W;
   const float* zeros;              // >= 16 B of zeros in device memory (source of out-of-image halo lines)
   int nsplit;                      // set by launch_gdfn_out: blocks per pixel tile, each owning C/nsplit outputs
+  int split;                       // non-zero: C = 192 / 384 as C / 96 blocks of the C = 96 kernel per pixel tile
+                                   // (KDLAE_DEBUG=gdfn_split; the same bits as the default gdfn_once_kernel)
 };
 bool gdfn_supported(int C, int hidS);
 hipError_t launch_gdfn_out(const GdfnParams& p, int C, hipStream_t s);

@@ -654,6 +654,7 @@ extern "C" int kdlae_debug_infer(const kdlae_debug_infer_desc* d, void* stream) 
       p.x = d->in[0]; p.ld = d->ldi[0]; p.hidS = d->hidS; p.dw = d->w[0]; p.Wp = sc.p[0]; p.bias = d->bias[0];
       p.R = d->R; p.ldr = d->ldr; p.out = d->out[0]; p.ldo = d->ldo[0];
       p.Bn = d->Bn; p.H = d->H; p.W = d->W; p.zeros = d->zeros;
+      p.split = d->out_mode != 0;
       e = kdlae::launch_gdfn_out(p, C, s);
       break;
     }
