@@ -388,6 +388,31 @@ int kdlae_tt_mark_count(const kdlae_tt_handle* h);
 int64_t kdlae_tt_mark_lo(const kdlae_tt_handle* h, int j);
 int kdlae_tt_mark_wait(kdlae_tt_handle* h, int j, void* stream);
 int kdlae_tt_mark_sync(kdlae_tt_handle* h, int j);
+/* Fine-tuning with frozen parameters (the reference's freeze_except_patch_embed_and_enhance,
+ * Train/basicsr/train.py:24-55, and the requires_grad filter of ImageCleanModel.setup_optimizers).
+ * mask: host array of kdlae_tt_num_params(h) bytes in state_dict order, nonzero = trainable; NULL = all
+ * (the default: exactly the launches of a handle that never saw a mask).  n != num_params, or a mask
+ * that marks no key the forward uses, is KDLAE_EINVAL_CONFIG; a call between a kdlae_tt_forward and its
+ * backward is KDLAE_ESTATE.  Keys the forward never touches (output_param.*, refinement_out.* when
+ * params != 'cat') are ignored.  The mask holds for every later forward and backward until it is
+ * changed; a change invalidates the last forward (a backward needs a new one).
+ * Under a mask, with the layers in forward order (patch_embed, encoder_level1, ..., refinement, output,
+ * output_param, refinement_out, output2, cen, upen, enhance, outputen; inside a TransformerBlock norm1,
+ * attn.qkv, attn.qkv_dwconv, attn.temperature, attn.project_out, norm2, ffn.project_in, ffn.dwconv,
+ * ffn.project_out): a layer's weight gradient is computed iff its key is trainable, its input gradient
+ * iff a trainable key belongs to an earlier layer; the forward keeps no activations of the
+ * TransformerBlocks before the first trainable key, and kdlae_tt_workspace_bytes answers for the
+ * current mask (the workspace contract above holds under every mask).  After a backward every float of
+ * a frozen key and every pad float of `grad` is +0.0f, so kdlae_train_clip_adamw's norm over all n
+ * floats is the norm over the trainable ones, and every float of a trainable key has the bits the
+ * all-trainable backward gives on the same inputs; hq / sr have the same bits under every mask.  The
+ * gradient-ready marks stay valid: a frozen key holds the zero fill, which precedes every mark.
+ * kdlae_tt_is_trainable: 1 / 0 for key `index` under the current mask, -1 for a bad index. */
+int kdlae_tt_set_trainable(kdlae_tt_handle* h, const unsigned char* mask, int n);
+int kdlae_tt_is_trainable(const kdlae_tt_handle* h, int index);
+/* Launch calls the last kdlae_tt_backward / _backward_marked issued: kernels (a split-K GEMM with its
+ * reduction counts once), memsets and memcpys, the zero fill of `grad` included.  For tests and probes. */
+int64_t kdlae_tt_debug_backward_launches(const kdlae_tt_handle* h);
 
 /* replaces self.cri_pix(pred, self.gt) with L1LossSr(loss_weight=1, reduction='mean') (losses.py:159-170):
  * loss[0] = 0.5 l1(hq) + 0.25 l1(sr) + 0.25 (shadow(hq) + shadow(sr)); dhq / dsr receive its gradient
@@ -844,7 +869,13 @@ int kdlae_debug_head_train(const kdlae_debug_head_train_desc* d, void* stream);
  *   op 12 copy_cols     in0 [P][ldi0] -> out0 [P][ldo0], C columns (accumulate), zero_to
  *   op 13 nchw_to_nhwc  in0 [Bn][C][P] -> out0 [Bn P][ldo0] (accumulate)
  *   op 14 nhwc_to_nchw  in0 [Bn P][ldi0] (+ in1 = add [Bn][C][P] or null) -> out0 [Bn][C][P]
- *   op 15 pack_w3       w = OIHW 3x3 weight, C = Cg, C2 = N, flag = mode (2 or 3) -> out0 [9 Cg][N] */
+ *   op 15 pack_w3       w = OIHW 3x3 weight, C = Cg, C2 = N, flag = mode (2 or 3) -> out0 [9 Cg][N]
+ *   op 16 dwgate_bwd_dx, 17 dwgate_bwd_rc_dx, 18 dw_bwd_dx: the operands of ops 4, 5, 6 -> out0 = dy alone, by
+ *                       the kernels' dx-only variants (frozen dwconv weights: no weight-gradient partials;
+ *                       same dy bits); part is ignored and may be null; op 18 does not read in1
+ *   op 19 ln_bwd_dx     in0 = dy, in1 = x, in2 = stats [P][2], in3 = R (or null), w, C <= 512, P, nblk = blocks
+ *                       -> out0 = dx (+ R): LayerNorm backward without the weight / bias partials (same dx bits
+ *                       as kdlae_debug_ln dir 1); flag bit 0 = biasfree, bit 1 = route 1 (the generic kernel) */
 typedef struct kdlae_debug_train_red {
   const float* part; float* out;
   int nblk, ncols, pstride;

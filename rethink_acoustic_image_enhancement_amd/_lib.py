@@ -39,6 +39,7 @@ EXPORTS = (
     "kdlae_tt_create", "kdlae_tt_destroy", "kdlae_tt_num_params", "kdlae_tt_param_info", "kdlae_tt_num_floats",
     "kdlae_tt_workspace_bytes", "kdlae_tt_forward", "kdlae_tt_backward", "kdlae_tt_backward_marked",
     "kdlae_tt_mark_count", "kdlae_tt_mark_lo", "kdlae_tt_mark_wait", "kdlae_tt_mark_sync",
+    "kdlae_tt_set_trainable", "kdlae_tt_is_trainable", "kdlae_tt_debug_backward_launches",
     "kdlae_train_l1sr_scratch_floats", "kdlae_train_l1sr", "kdlae_train_adamw_scratch_floats",
     "kdlae_train_clip_adamw", "kdlae_train_mixup", "kdlae_train_ema",
     "kdlae_st_create", "kdlae_st_destroy", "kdlae_st_num_params", "kdlae_st_param_info", "kdlae_st_num_floats",
@@ -289,6 +290,10 @@ def lib() -> ctypes.CDLL:
     L.kdlae_tt_mark_lo.restype = c_int64
     L.kdlae_tt_mark_wait.argtypes = [c_void_p, c_int, c_void_p]
     L.kdlae_tt_mark_sync.argtypes = [c_void_p, c_int]
+    L.kdlae_tt_set_trainable.argtypes = [c_void_p, c_void_p, c_int]
+    L.kdlae_tt_is_trainable.argtypes = [c_void_p, c_int]
+    L.kdlae_tt_debug_backward_launches.argtypes = [c_void_p]
+    L.kdlae_tt_debug_backward_launches.restype = c_int64
     L.kdlae_train_l1sr_scratch_floats.argtypes = []
     L.kdlae_train_l1sr_scratch_floats.restype = c_int64
     L.kdlae_train_l1sr.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
@@ -364,7 +369,8 @@ def lib() -> ctypes.CDLL:
     L.kdlae_debug_gemm_variant.argtypes = [c_int, c_int, ctypes.POINTER(c_int)]
     for name in EXPORTS:
         if not name.endswith(("_last_error", "_abi_version", "_workspace_bytes", "_padded_size", "_num_floats",
-                              "_scratch_floats", "_scratch_bytes", "_params_numel", "_mark_lo", "_num_stat_floats")):
+                              "_scratch_floats", "_scratch_bytes", "_params_numel", "_mark_lo", "_num_stat_floats",
+                              "_backward_launches")):
             getattr(L, name).restype = c_int
     _lib = L
     return L

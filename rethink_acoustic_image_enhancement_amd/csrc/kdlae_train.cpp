@@ -88,6 +88,31 @@ struct kdlae_tt_handle : kdlae::TrainHandleBase {
   // stage_bwd's lagged synchronisation: recorded after each block's last side launch (its scratch
   // region and gradient buffers are reused two blocks later)
   hipEvent_t ev_blk[2] = {nullptr, nullptr};
+  // Fine-tuning (kdlae_tt_set_trainable).  `pos`: every layer of the forward (a key without its
+  // ".weight" / ".bias"; attn.temperature is its own layer) -> its place in forward order; keys the
+  // forward never touches have none.  `stage_rng`: the [first, end) places of a stage's blocks.
+  // `mask`: one byte per key, empty = every key trainable.  `frontier`: the first place that holds
+  // a trainable key; the backward stops there and the forward saves nothing before it.
+  std::unordered_map<std::string, int> pos;
+  std::unordered_map<std::string, std::pair<int, int>> stage_rng;
+  std::vector<unsigned char> mask;
+  int frontier = 0;
+  bool fwd_open = false;          // a forward whose backward has not run yet
+  int64_t bwd_launches = 0;       // launches of the last backward (kdlae_tt_debug_backward_launches)
+  int pos_of(const std::string& layer) const {
+    auto it = pos.find(layer);
+    return it == pos.end() ? -1 : it->second;
+  }
+  // the layer takes part in the backward (its own gradient or a trainable key before it)
+  bool live(const std::string& layer) const { return frontier <= pos_of(layer); }
+  // the gradient of the layer's input is needed: a trainable key lies before it in forward order
+  bool need_dx(const std::string& layer) const { return frontier < pos_of(layer); }
+  bool stage_live(const std::string& stage) const { return frontier < stage_rng.at(stage).second; }
+  bool stage_dx(const std::string& stage) const { return frontier < stage_rng.at(stage).first; }
+  bool trainable(const std::string& key) const {
+    auto it = lay.index.find(key);
+    return it != lay.index.end() && (mask.empty() || mask[it->second]);
+  }
   ~kdlae_tt_handle() override {
     for (hipEvent_t e : mark_ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : ev_blk)
@@ -140,6 +165,8 @@ struct Ctx {
   float* splitk_main = nullptr;
   float* splitk_side = nullptr;
   bool in_side = false, side_pending = false;
+  long side_forks = 0;    // side segments opened on the side stream so far
+  int64_t nlaunch = 0;    // launches issued (LAUNCH), for kdlae_tt_debug_backward_launches
   // gradient-ready marks (kdlae_tt_backward_marked): the dry run records, per key offset, the first
   // and last mark index at which its gradient was written; the real run records an event per mark
   TouchMap* touch = nullptr;
@@ -172,7 +199,10 @@ struct Ctx {
     const int64_t o = h->lay.find(k);
     return o < 0 ? nullptr : th + o;
   }
+  bool T(const std::string& k) const { return h->trainable(k); }  // the key exists and is trainable
+  // a key's gradient; null for a key the model lacks and for a frozen one (it keeps the zero fill)
   float* G(const std::string& k) const {
+    if (!h->trainable(k)) return nullptr;
     const int64_t o = h->lay.find(k);
     if (o < 0) return nullptr;
     if (touch) {
@@ -199,6 +229,7 @@ int side_begin(Ctx& c) {
   TRY(c.side->fork(c.main_s));
   c.s = c.side->s;
   c.side_pending = true;
+  ++c.side_forks;
   return KDLAE_OK;
 }
 
@@ -293,7 +324,8 @@ void trace_end(Ctx& c, hipEvent_t a, const char* what) {
     if (!c.dry) {                                                                                    \
       hipEvent_t ta_ = c.trace ? trace_begin(c) : nullptr;                                           \
       hipError_t e_ = (x);                                                                           \
-      if (c.trace) trace_end(c, ta_, #x);                                                            \
+      ++c.nlaunch;                                                                                   \
+      if (c.trace) trace_end(c, ta_, #x);                                                          \
       if (e_ != hipSuccess) return fail(KDLAE_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
     }                                                                                                \
   } while (0)
@@ -417,16 +449,21 @@ int bias_grad(Ctx& c, V dy, int N, long long P, float* out) {
 // dW = dY^T X, db = colsum dY, dX = dY W (+R)
 int conv1_bwd(Ctx& c, const std::string& n, V x, V dy, int Cin, int Cout, long long P, V dx, const float* R = nullptr,
               int ldr = 0, V wp = {nullptr, 0}, bool pad_ok = false) {
-  tr::TGemm g;
-  g.A = dy.p; g.sam = 1; g.sak = dy.ld;
-  g.B = x.p; g.sbk = x.ld; g.sbn = 1;
-  g.C = c.G(n + ".weight"); g.scm = Cin; g.scn = 1;
-  g.M = Cout; g.N = Cin; g.K = (int)P;
-  TRY(side_begin(c));  // dW and db only read x and dy
-  g.partial = c.splitk;
-  TRY(gemm(c, g, kSplitCap, n + " dW"));
-  TRY(bias_grad(c, dy, Cout, P, c.G(n + ".bias")));
-  side_end(c);
+  const bool tw = c.T(n + ".weight"), tb = c.T(n + ".bias");  // a frozen key: no launch for it
+  if (tw || tb) {
+    TRY(side_begin(c));  // dW and db only read x and dy
+    if (tw) {
+      tr::TGemm g;
+      g.A = dy.p; g.sam = 1; g.sak = dy.ld;
+      g.B = x.p; g.sbk = x.ld; g.sbn = 1;
+      g.C = c.G(n + ".weight"); g.scm = Cin; g.scn = 1;
+      g.M = Cout; g.N = Cin; g.K = (int)P;
+      g.partial = c.splitk;
+      TRY(gemm(c, g, kSplitCap, n + " dW"));
+    }
+    if (tb) TRY(bias_grad(c, dy, Cout, P, c.G(n + ".bias")));
+    side_end(c);
+  }
   if (dx.p) {
     tr::TGemm d;
     d.A = dy.p; d.sam = dy.ld; d.sak = 1;
@@ -526,23 +563,26 @@ int conv3(Ctx& c, const std::string& n, V x, int Cin, int Cout, int Bn, int H, i
 int conv3_bwd(Ctx& c, const std::string& n, V x, V dy, int Cin, int Cout, int Bn, int H, int W, int dil, V dx,
               const float* R = nullptr, int ldr = 0) {
   const long long P = (long long)Bn * H * W;
-  float* gw = c.G(n + ".weight");
-  TRY(side_begin(c));  // dW and db only read x and dy (dx may alias R, never x or dy)
-  if (tr::dw3_small_ok(Cin, Cout) && gw) {
-    // narrow side: per-block [Cout][Cin][9] partials on the VALU (train_small.hip)
-    const int ncols = Cin * Cout * 9;
-    const int nb = tr::dw3_small_blocks(P, Cin, Cout, c.red_cap);
-    float* part = red_take(c, (size_t)nb * ncols);
-    if (!part) return c.red_err;
-    LAUNCH(tr::launch_dw3_small(dy.p, dy.ld, x.p, x.ld, Cin, Cout, Bn, H, W, dil, part, nb, c.s));
-    TRY(queue_reduce(c, part, nb, ncols, ncols, gw));
-  } else {
-    tr::TGemm g = tr::conv3_dw_gemm({dy.p, dy.ld, Cout}, {x.p, x.ld, Cin}, gw, {Bn, H, W, dil});
-    g.partial = c.splitk;
-    TRY(gemm(c, g, kSplitCap, n + " dW3"));
+  const bool tw = c.T(n + ".weight"), tb = c.T(n + ".bias");  // a frozen key: no launch for it
+  if (tw || tb) {
+    float* gw = tw ? c.G(n + ".weight") : nullptr;
+    TRY(side_begin(c));  // dW and db only read x and dy (dx may alias R, never x or dy)
+    if (tw && tr::dw3_small_ok(Cin, Cout) && gw) {
+      // narrow side: per-block [Cout][Cin][9] partials on the VALU (train_small.hip)
+      const int ncols = Cin * Cout * 9;
+      const int nb = tr::dw3_small_blocks(P, Cin, Cout, c.red_cap);
+      float* part = red_take(c, (size_t)nb * ncols);
+      if (!part) return c.red_err;
+      LAUNCH(tr::launch_dw3_small(dy.p, dy.ld, x.p, x.ld, Cin, Cout, Bn, H, W, dil, part, nb, c.s));
+      TRY(queue_reduce(c, part, nb, ncols, ncols, gw));
+    } else if (tw) {
+      tr::TGemm g = tr::conv3_dw_gemm({dy.p, dy.ld, Cout}, {x.p, x.ld, Cin}, gw, {Bn, H, W, dil});
+      g.partial = c.splitk;
+      TRY(gemm(c, g, kSplitCap, n + " dW3"));
+    }
+    if (tb) TRY(bias_grad(c, dy, Cout, P, c.G(n + ".bias")));
+    side_end(c);
   }
-  TRY(bias_grad(c, dy, Cout, P, c.G(n + ".bias")));
-  side_end(c);
   if (dx.p) {
     // the transposed conv: Cout -> Cin channels (flipped taps), narrow-side kernels where they apply
     int done = 0;
@@ -558,13 +598,17 @@ int conv3_bwd(Ctx& c, const std::string& n, V x, V dy, int Cin, int Cout, int Bn
 }
 
 // ---- TransformerBlock (KDLAE_model.py:150-163)
-int block_fwd(Ctx& c, BlockRec& r) {
+// keep = false (a block before the first trainable key: it has no backward): only the block's output
+// stays allocated; everything else is released when the block is done
+int block_fwd(Ctx& c, BlockRec& r, bool keep) {
   const kdlae_t_config& cf = c.h->cfg;
   const int C = r.C, C3 = 3 * C, hid = r.hid, heads = r.heads, Ch = C / heads, Bn = r.Bn;
   const long long HW = (long long)r.H * r.W, P = Bn * HW;
   const int bf = cf.layernorm_biasfree;
   const std::string& p = r.p;
   c.tag = p;
+  if (!keep) r.out = c.alloc(P * C);
+  const size_t release_to = c.off;
   r.xn1 = c.alloc(P * C);
   r.st1 = c.alloc(2 * P);
   LAUNCH(tr::launch_ln_fwd(r.x, C, c.W(p + ".norm1.body.weight"), c.W(p + ".norm1.body.bias"), C, P, bf, r.xn1, C,
@@ -621,7 +665,7 @@ int block_fwd(Ctx& c, BlockRec& r) {
   // dwconv + GELU gate in one pass (train_dwg.hip): g for project_out
   LAUNCH(tr::launch_dwgate_fwd(r.y, L2, c.W(p + ".ffn.dwconv.weight"), c.W(p + ".ffn.dwconv.bias"), hid, Bn, r.H,
                                r.W, r.yd, L2, r.g, L1, c.s));
-  r.out = c.alloc(P * C);
+  if (keep) r.out = c.alloc(P * C);
   if (hid % 4) {
     // row stride hid is not a multiple of 4 floats: a zero-padded [C][ld4(hid)] copy lets the forward
     // and dX GEMMs use the vectorised kernel (kept until the backward: theta is unchanged in between)
@@ -629,6 +673,7 @@ int block_fwd(Ctx& c, BlockRec& r) {
     LAUNCH(tr::launch_copy_cols(c.W(p + ".ffn.project_out.weight"), hid, r.wpo, L1, hid, C, 0, c.s, L1));
   }
   TRY(conv1(c, p + ".ffn.project_out", {r.g, L1}, hid, C, P, {r.out, C}, r.x1, C, {r.wpo, L1}));
+  if (!keep) c.off = release_to;
   return KDLAE_OK;
 }
 
@@ -636,8 +681,10 @@ int block_fwd(Ctx& c, BlockRec& r) {
 int dw_reduce(Ctx& c, const float* part, int nb, int C, const std::string& n) {
   // partial columns: [9 C weights | C bias]; one reduce when the bias key directly follows the
   // weight key in the flat buffer (keys are 16-byte aligned, so only when 9 C % 4 == 0)
-  float* gw = c.G(n + ".weight");
-  float* gb = c.G(n + ".bias");
+  const bool tw = c.T(n + ".weight"), tb = c.T(n + ".bias");  // a frozen key's columns are not summed
+  float* gw = tw ? c.G(n + ".weight") : nullptr;
+  float* gb = tb ? c.G(n + ".bias") : nullptr;
+  if (!tw) return tb ? queue_reduce(c, part + 9LL * C, nb, C, 10 * C, gb) : KDLAE_OK;
   if (!gb || gb == gw + 9LL * C) return queue_reduce(c, part, nb, gb ? 10 * C : 9 * C, 10 * C, gw);
   TRY(queue_reduce(c, part, nb, 9 * C, 10 * C, gw));
   return queue_reduce(c, part + 9LL * C, nb, C, 10 * C, gb);
@@ -650,42 +697,53 @@ int ln_bwd(Ctx& c, const float* dy, const float* x, const float* st, int C, long
   // 32 pixels per block (8 per wave: one or two steps of the lane-group loop, whose loads are used
   // right away, so the kernel is latency-bound and wants many waves in flight), up to 2048 blocks
   const int nb = nblk_for(P, ncol, KDLAE_LN_BWD_MAXB, KDLAE_LN_BWD_ROWS);
+  const bool tw = c.T(n + ".weight"), tb = !bf && c.T(n + ".bias");
+  if (!tw && !tb) {  // both frozen: the dx-only kernel (no partials, nothing to reduce)
+    LAUNCH(tr::launch_ln_bwd(dy, C, x, C, c.W(n + ".weight"), st, C, P, bf, R, C, dx, C, nullptr, nb, c.s));
+    return KDLAE_OK;
+  }
   float* part = red_take(c, (size_t)nb * ncol);
   if (!part) return c.red_err;
   LAUNCH(tr::launch_ln_bwd(dy, C, x, C, c.W(n + ".weight"), st, C, P, bf, R, C, dx, C, part, nb, c.s));
   // partial columns: [C weight | C bias (WithBias)], split when the keys are not adjacent
-  float* gw = c.G(n + ".weight");
-  float* gb = bf ? nullptr : c.G(n + ".bias");
-  if (!gb || gb == gw + C) return queue_reduce(c, part, nb, ncol, ncol, gw);
+  float* gw = tw ? c.G(n + ".weight") : nullptr;
+  float* gb = tb ? c.G(n + ".bias") : nullptr;
+  if (!tw) return queue_reduce(c, part + C, nb, C, ncol, gb);
+  if (!tb) return queue_reduce(c, part, nb, C, ncol, gw);
+  if (gb == gw + C) return queue_reduce(c, part, nb, ncol, ncol, gw);
   TRY(queue_reduce(c, part, nb, C, ncol, gw));
   return queue_reduce(c, part + C, nb, C, ncol, gb);
 }
 
-// d: [P][C] gradient of the block output on entry, of the block input on exit
 // d_in: [P][C] gradient of the block output; d_out: of the block input (a different buffer).
+// The layers run last to first and stop at the frontier (the first layer that holds a trainable
+// key): a layer's weight gradient is computed iff its key is trainable, its input gradient iff a
+// trainable key lies before it.  The layer at the frontier runs for its weight gradient alone.
 // Synchronisation with the side stream (stage_bwd passes lag = true): the main stream never waits for
 // the block's own side launches.  The side launches read d_in (project_out weight gradient) and this
 // block's scratch (the dW GEMMs' dy, dx1, dqkv and the bias sums); stage_bwd rotates three gradient
 // buffers and alternates two scratch regions, so neither is written again before the block after
 // next, whose start waits for this block's side launches.  lag = false: a join before the last
-// LayerNorm backward and a full flush + join at the end.  *extent: end of the block's scratch.
-int block_bwd(Ctx& c, const BlockRec& r, const float* d_in, float* d_out, bool lag, size_t* extent) {
+// LayerNorm backward and a full flush + join at the end.
+int block_bwd_layers(Ctx& c, const BlockRec& r, const float* d_in, float* d_out, bool lag) {
   float* d = const_cast<float*>(d_in);
+  const kdlae_tt_handle& h = *c.h;
   const int C = r.C, C3 = 3 * C, hid = r.hid, heads = r.heads, Ch = C / heads, Bn = r.Bn;
   const long long HW = (long long)r.H * r.W, P = Bn * HW;
   const std::string& p = r.p;
-  c.tag = p;
-  const size_t mark = c.off;
   // ffn (KDLAE_model.py:101-106)
   const int L2 = ld4(2 * hid), L1 = ld4(hid);
-  float* dg = c.alloc(P * L1);
+  const bool x_po = h.need_dx(p + ".ffn.project_out");
+  float* dg = x_po ? c.alloc(P * L1) : nullptr;
   TRY(conv1_bwd(c, p + ".ffn.project_out", {r.g, L1}, {d, C}, hid, C, P, {dg, L1}, nullptr, 0, {r.wpo, L1}, true));
+  if (!x_po) return KDLAE_OK;
   float* dy = c.alloc(P * L2);
   {
-    // gate backward + transposed dwconv + dwconv weight gradient in one pass (train_dwg.hip)
+    // gate backward + transposed dwconv (+ dwconv weight gradient, unless frozen) in one pass (train_dwg.hip)
+    const bool dw = c.T(p + ".ffn.dwconv.weight") || c.T(p + ".ffn.dwconv.bias");
     const int nb = tr::dwg_blocks(Bn, r.H, r.W);
-    float* part = red_take(c, (size_t)nb * 10 * 2 * hid);
-    if (!part) return c.red_err;
+    float* part = dw ? red_take(c, (size_t)nb * 10 * 2 * hid) : nullptr;
+    if (dw && !part) return c.red_err;
     if (r.yd) {
       LAUNCH(tr::launch_dwgate_bwd(dg, L1, r.yd, L2, r.y, L2, c.W(p + ".ffn.dwconv.weight"), hid, Bn, r.H, r.W, dy,
                                    L2, part, c.s));
@@ -693,18 +751,25 @@ int block_bwd(Ctx& c, const BlockRec& r, const float* d_in, float* d_out, bool l
       LAUNCH(tr::launch_dwgate_bwd_rc(dg, L1, r.y, L2, c.W(p + ".ffn.dwconv.weight"), c.W(p + ".ffn.dwconv.bias"), hid,
                                       Bn, r.H, r.W, dy, L2, part, c.s));
     }
-    TRY(dw_reduce(c, part, nb, 2 * hid, p + ".ffn.dwconv"));
+    if (dw) TRY(dw_reduce(c, part, nb, 2 * hid, p + ".ffn.dwconv"));
   }
-  float* dxn2 = c.alloc(P * C);
+  if (!h.need_dx(p + ".ffn.dwconv")) return KDLAE_OK;
+  const bool x_pi = h.need_dx(p + ".ffn.project_in");
+  float* dxn2 = x_pi ? c.alloc(P * C) : nullptr;
   TRY(conv1_bwd(c, p + ".ffn.project_in", {r.xn2, C}, {dy, L2}, C, 2 * hid, P, {dxn2, C}));
+  if (!x_pi) return KDLAE_OK;
   float* dx1 = c.alloc(P * C);
   TRY(ln_bwd(c, dxn2, r.x1, r.st2, C, P, p + ".norm2.body", d, dx1));
+  if (!h.need_dx(p + ".norm2.body")) return KDLAE_OK;
   // attention (KDLAE_model.py:124-145)
-  float* dao = c.alloc(P * C);
+  const bool x_ao = h.need_dx(p + ".attn.project_out");
+  float* dao = x_ao ? c.alloc(P * C) : nullptr;
   TRY(conv1_bwd(c, p + ".attn.project_out", {r.ao, C}, {dx1, C}, C, C, P, {dao, C}));
+  if (!x_ao) return KDLAE_OK;
+  const bool x_sm = h.need_dx(p + ".attn.temperature");  // dq, dk, dv
   const size_t mats = (size_t)Bn * heads * Ch * Ch;
   float* dA = c.alloc(mats);
-  float* dqkvd = c.alloc(P * C3);
+  float* dqkvd = x_sm ? c.alloc(P * C3) : nullptr;
   {
     tr::TGemm g;  // dA[i,j] = sum_p dao[p,i] v[p,j]
     g.A = dao; g.sam = 1; g.sak = C; g.bA1 = HW * C; g.bA2 = Ch;
@@ -714,7 +779,7 @@ int block_bwd(Ctx& c, const BlockRec& r, const float* d_in, float* d_out, bool l
     g.partial = c.splitk;
     TRY(gemm(c, g, kSplitCap, "dA"));
   }
-  {
+  if (x_sm) {
     tr::TGemm g;  // dv[p,j] = sum_i dao[p,i] A[i,j]
     g.A = dao; g.sam = C; g.sak = 1; g.bA1 = HW * C; g.bA2 = Ch;
     g.B = r.A; g.sbk = Ch; g.sbn = 1; g.bB1 = (long long)heads * Ch * Ch; g.bB2 = (long long)Ch * Ch;
@@ -728,7 +793,8 @@ int block_bwd(Ctx& c, const BlockRec& r, const float* d_in, float* d_out, bool l
   float* dtp = c.alloc((size_t)Bn * heads);
   LAUNCH(tr::launch_attn_bwd(r.G, r.sumsq, c.W(p + ".attn.temperature"), r.A, dA, Bn, C, heads, Mq, cq, ck, dtp, c.s));
   float* gtemp = c.G(p + ".attn.temperature");  // outside LAUNCH: the dry run must record the write
-  TRY(queue_reduce(c, dtp, Bn, heads, heads, gtemp));
+  if (c.T(p + ".attn.temperature")) TRY(queue_reduce(c, dtp, Bn, heads, heads, gtemp));
+  if (!x_sm) return KDLAE_OK;
   {
     tr::TGemm g;  // dq[p,i] = sum_j Mq[i,j] k[p,j] + cq[i] q[p,i]
     g.A = r.qkvd + C; g.sam = C3; g.sak = 1; g.bA1 = HW * C3; g.bA2 = Ch;
@@ -747,17 +813,30 @@ int block_bwd(Ctx& c, const BlockRec& r, const float* d_in, float* d_out, bool l
   }
   float* dqkv = c.alloc(P * C3);
   {
+    // frozen qkv_dwconv: the dx-only kernel, which does not read the layer input qkv
+    const bool dw = c.T(p + ".attn.qkv_dwconv.weight") || c.T(p + ".attn.qkv_dwconv.bias");
     const int nb = tr::dwg_blocks(Bn, r.H, r.W);
-    float* part = red_take(c, (size_t)nb * 10 * C3);
-    if (!part) return c.red_err;
-    LAUNCH(tr::launch_dw_bwd(dqkvd, C3, r.qkv, C3, c.W(p + ".attn.qkv_dwconv.weight"), C3, Bn, r.H, r.W, dqkv, C3,
-                             part, c.s));
-    TRY(dw_reduce(c, part, nb, C3, p + ".attn.qkv_dwconv"));
+    float* part = dw ? red_take(c, (size_t)nb * 10 * C3) : nullptr;
+    if (dw && !part) return c.red_err;
+    LAUNCH(tr::launch_dw_bwd(dqkvd, C3, dw ? r.qkv : nullptr, C3, c.W(p + ".attn.qkv_dwconv.weight"), C3, Bn, r.H, r.W,
+                             dqkv, C3, part, c.s));
+    if (dw) TRY(dw_reduce(c, part, nb, C3, p + ".attn.qkv_dwconv"));
   }
-  float* dxn1 = c.alloc(P * C);
+  if (!h.need_dx(p + ".attn.qkv_dwconv")) return KDLAE_OK;
+  const bool x_qkv = h.need_dx(p + ".attn.qkv");
+  float* dxn1 = x_qkv ? c.alloc(P * C) : nullptr;
   TRY(conv1_bwd(c, p + ".attn.qkv", {r.xn1, C}, {dqkv, C3}, C, C3, P, {dxn1, C}));
+  if (!x_qkv) return KDLAE_OK;
   if (!lag) TRY(join(c));
   TRY(ln_bwd(c, dxn1, r.x, r.st1, C, P, p + ".norm1.body", dx1, d_out));
+  return KDLAE_OK;
+}
+
+// the block's layers, then the end of the block; *extent: end of the block's scratch
+int block_bwd(Ctx& c, const BlockRec& r, const float* d_in, float* d_out, bool lag, size_t* extent) {
+  c.tag = r.p;
+  const size_t mark = c.off;
+  TRY(block_bwd_layers(c, r, d_in, d_out, lag));
   TRY(flush_reduce(c));  // the main list, before the block's scratch (dtp) is released
   if (!lag) TRY(flush_all(c));
   if (extent) *extent = c.off;
@@ -773,7 +852,7 @@ int stage_fwd(Ctx& c, const std::string& name, int n, int C, int heads, int Bn, 
     r.p = name + "." + std::to_string(i);
     r.C = C; r.heads = heads; r.hid = hid_of(c.h->cfg, C); r.Bn = Bn; r.H = H; r.W = W;
     r.x = x;
-    TRY(block_fwd(c, r));
+    TRY(block_fwd(c, r, c.h->live(r.p + ".ffn.project_out")));
     x = r.out;
   }
   *out = x;
@@ -789,6 +868,7 @@ int stage_fwd(Ctx& c, const std::string& name, int n, int C, int heads, int Bn, 
 // gradient-ready marks need them); the stage ends with one either way, the result copied into d.
 int stage_bwd(Ctx& c, const std::string& name, float* d) {
   const auto& recs = c.h->sv.stages.at(name);
+  if (recs.empty() || !c.h->stage_live(name)) return KDLAE_OK;
   const bool lag = !c.record_marks && !c.dry && c.side && KDLAE_TRAIN_LAG;
   const BlockRec& r0 = recs.front();
   const size_t dn = (size_t)r0.Bn * r0.H * r0.W * r0.C;
@@ -797,24 +877,32 @@ int stage_bwd(Ctx& c, const std::string& name, float* d) {
   const size_t base = c.off;
   size_t e0 = base;
   c.blk_rec[0] = c.blk_rec[1] = false;
-  for (int i = (int)recs.size() - 1, k = 0; i >= 0; --i, ++k) {
+  int k = 0;
+  // last block first, down to the block that holds the frontier (fine-tuning; else block 0)
+  for (int i = (int)recs.size() - 1; i >= 0 && c.h->live(recs[i].p + ".ffn.project_out"); --i, ++k) {
     const int par = k & 1;
     c.off = par ? e0 : base;  // the same layout with or without lag, so the dry run sizes it
     if (lag && c.blk_rec[par]) TRY(main_wait(c, c.h->ev_blk[par]));
     size_t ext = 0;
+    const long forks = c.side_forks;
     TRY(block_bwd(c, recs[i], dbuf[k % 3], dbuf[(k + 1) % 3], lag, &ext));
     if (par == 0) e0 = ext;
     if (lag) {
-      TRY(side_record(c, c.h->ev_blk[par]));
-      c.blk_rec[par] = true;
+      // a block without side launches (every weight in it frozen) has nothing a later block must wait for
+      if (c.side_forks != forks) {
+        TRY(side_record(c, c.h->ev_blk[par]));
+        c.blk_rec[par] = true;
+      }
       ++c.cur_mark;  // mark() without its flush and join
     } else {
       TRY(mark(c));
     }
   }
   if (lag) TRY(flush_all(c));
-  const float* res = dbuf[recs.size() % 3];
-  if (res != d) LAUNCH(hipMemcpyAsync(d, res, dn * sizeof(float), hipMemcpyDeviceToDevice, c.s));
+  // the stage's input gradient, unless the frontier lies inside the stage (nobody reads it then)
+  const float* res = dbuf[k % 3];
+  if (res != d && c.h->stage_dx(name))
+    LAUNCH(hipMemcpyAsync(d, res, dn * sizeof(float), hipMemcpyDeviceToDevice, c.s));
   c.off = off0;
   return KDLAE_OK;
 }
@@ -909,102 +997,170 @@ int net_fwd(Ctx& c, const float* img, const float* rate, float* hq, float* sr) {
   return KDLAE_OK;
 }
 
-// has_dsr: the sr branch is differentiated (dsr given); the dry sizing pass always takes it
+// The sr branch (KDLAE_model.py:324-329), last layer first, down to the frontier; cen's input gradient
+// is added to dhq_h when a trainable key lies before cen (`trunk`).
+int sr_bwd(Ctx& c, const float* dsr, float* dhq_h) {
+  const kdlae_tt_handle& h = *c.h;
+  const Saved& s = h.sv;
+  const kdlae_t_config& cf = h.cfg;
+  const int B = s.B, H = s.H, W = s.W, d = cf.dim, oc = cf.out_channels, hc = 2 * d;
+  const long long P1 = (long long)B * H * W;
+  float* dsr_h = c.alloc(P1 * 4 * oc);
+  LAUNCH(tr::launch_nchw_to_nhwc(dsr, oc, B, 4LL * H * W, dsr_h, oc, 0, c.s));
+  const bool x_oe = h.need_dx("outputen");
+  float* denh = x_oe ? c.alloc(P1 * 4 * (hc / 2)) : nullptr;
+  TRY(conv3_bwd(c, "outputen", {s.enh, hc / 2}, {dsr_h, oc}, hc / 2, oc, B, 2 * H, 2 * W, 1, {denh, hc / 2}));
+  TRY(mark(c));
+  if (!x_oe) return KDLAE_OK;
+  TRY(stage_bwd(c, "enhance", denh));
+  if (!h.stage_dx("enhance")) return KDLAE_OK;
+  float* dupc = c.alloc(P1 * 2 * hc);
+  LAUNCH(tr::launch_shuffle(denh, hc / 2, dupc, 2 * hc, hc / 2, B, H, W, 0, c.s));
+  // upen's input (cenc) is recomputed-free: it was saved in the forward
+  const bool x_up = h.need_dx("upen.body.0");
+  float* dcen = x_up ? c.alloc(P1 * hc) : nullptr;
+  TRY(conv3_bwd(c, "upen.body.0", {s.cenc, hc}, {dupc, 2 * hc}, hc, 2 * hc, B, H, W, 1, {dcen, hc}));
+  TRY(mark(c));
+  if (!x_up) return KDLAE_OK;
+  const bool x_cen = h.need_dx("cen");
+  TRY(conv3_bwd(c, "cen", {s.hq_h, oc}, {dcen, hc}, oc, hc, B, H, W, 1, {x_cen ? dhq_h : nullptr, oc}, dhq_h, oc));
+  TRY(mark(c));
+  return KDLAE_OK;
+}
+
+// has_dsr: the sr branch is differentiated (dsr given); the dry sizing pass always takes it.
+// The plan (kdlae_tt_set_trainable; with no mask every condition below holds and the launches are
+// the all-trainable backward's): the layers run last to first and stop at the frontier, the first
+// layer in forward order that holds a trainable key.  A layer's weight gradient is computed iff its
+// key is trainable (conv*_bwd, ln_bwd, dw_reduce ask per key), its input gradient iff a trainable
+// key lies before it (need_dx / stage_dx); a skip gradient d(enc_i) is formed iff the frontier is at
+// or before the encoder stage that produced enc_i, which is when the Downsample after it, which
+// accumulates into it, has an input gradient.
 int net_bwd(Ctx& c, const float* dhq, const float* dsr, bool has_dsr) {
-  const Saved& s = c.h->sv;
-  const kdlae_t_config& cf = c.h->cfg;
+  const kdlae_tt_handle& h = *c.h;
+  const Saved& s = h.sv;
+  const kdlae_t_config& cf = h.cfg;
   const int B = s.B, H = s.H, W = s.W, d = cf.dim, oc = cf.out_channels, ic = cf.inp_channels;
   const long long P1 = (long long)B * H * W, P2 = P1 / 4, P3 = P1 / 16, P4 = P1 / 64;
   const int H2 = H / 2, W2 = W / 2, H3 = H / 4, W3 = W / 4, H4 = H / 8, W4 = W / 8;
 
   c.tag = "net";
-  float* dhq_h = c.alloc(P1 * oc);
-  if (dhq) LAUNCH(tr::launch_nchw_to_nhwc(dhq, oc, B, (long long)H * W, dhq_h, oc, 0, c.s));
-  else LAUNCH(hipMemsetAsync(dhq_h, 0, P1 * oc * sizeof(float), c.s));
+  // the trunk and the rate tail take part iff a trainable key lies at or before the hq head
+  const bool trunk = h.live(cf.params_cat ? "output2" : "output");
+  float* dhq_h = nullptr;
+  if (trunk) {
+    dhq_h = c.alloc(P1 * oc);
+    if (dhq) LAUNCH(tr::launch_nchw_to_nhwc(dhq, oc, B, (long long)H * W, dhq_h, oc, 0, c.s));
+    else LAUNCH(hipMemsetAsync(dhq_h, 0, P1 * oc * sizeof(float), c.s));
+  }
   if (cf.static_train && has_dsr) {
-    const int hc = 2 * d;
-    float* dsr_h = c.alloc(P1 * 4 * oc);
-    LAUNCH(tr::launch_nchw_to_nhwc(dsr, oc, B, 4LL * H * W, dsr_h, oc, 0, c.s));
-    float* denh = c.alloc(P1 * 4 * (hc / 2));
-    TRY(conv3_bwd(c, "outputen", {s.enh, hc / 2}, {dsr_h, oc}, hc / 2, oc, B, 2 * H, 2 * W, 1, {denh, hc / 2}));
-    TRY(mark(c));
-    TRY(stage_bwd(c, "enhance", denh));
-    float* dupc = c.alloc(P1 * 2 * hc);
-    LAUNCH(tr::launch_shuffle(denh, hc / 2, dupc, 2 * hc, hc / 2, B, H, W, 0, c.s));
-    // upen's input (cenc) is recomputed-free: it was saved in the forward
-    float* dcen = c.alloc(P1 * hc);
-    TRY(conv3_bwd(c, "upen.body.0", {s.cenc, hc}, {dupc, 2 * hc}, hc, 2 * hc, B, H, W, 1, {dcen, hc}));
-    TRY(mark(c));
-    TRY(conv3_bwd(c, "cen", {s.hq_h, oc}, {dcen, hc}, oc, hc, B, H, W, 1, {dhq_h, oc}, dhq_h, oc));
-    TRY(mark(c));
+    TRY(sr_bwd(c, dsr, dhq_h));
   } else if (cf.static_train) {
     // sr unused by the loss: its parameters get zero gradients (grad buffer is zeroed up front)
   }
+  if (!trunk) return KDLAE_OK;  // only sr-head keys are trainable
   // hq = out + img: d(out) = dhq
-  float* dref = c.alloc(P1 * 2 * d);
+  const bool x_out = h.need_dx("output");
+  float* dref = x_out ? c.alloc(P1 * 2 * d) : nullptr;
   if (cf.params_cat) {
-    float* dro = c.alloc(P1 * 2 * d);
+    const bool x_o2 = h.need_dx("output2");
+    float* dro = x_o2 ? c.alloc(P1 * 2 * d) : nullptr;
     TRY(conv3_bwd(c, "output2", {s.ro, 2 * d}, {dhq_h, oc}, 2 * d, oc, B, H, W, 1, {dro, 2 * d}));
     TRY(mark(c));
+    if (!x_o2) return KDLAE_OK;
     TRY(stage_bwd(c, "refinement_out", dro));
-    float* dcatp = c.alloc(P1 * (oc + 1));
+    if (!h.stage_dx("refinement_out")) return KDLAE_OK;
+    const bool x_op = h.need_dx("output_param");
+    float* dcatp = x_op ? c.alloc(P1 * (oc + 1)) : nullptr;
     TRY(conv3_bwd(c, "output_param", {s.catp, oc + 1}, {dro, 2 * d}, oc + 1, 2 * d, B, H, W, 2, {dcatp, oc + 1}));
     TRY(mark(c));
+    if (!x_op) return KDLAE_OK;
     TRY(conv3_bwd(c, "output", {s.ref, 2 * d}, {dcatp, oc + 1}, 2 * d, oc, B, H, W, 1, {dref, 2 * d}));
     TRY(mark(c));
   } else {
     TRY(conv3_bwd(c, "output", {s.ref, 2 * d}, {dhq_h, oc}, 2 * d, oc, B, H, W, 1, {dref, 2 * d}));
     TRY(mark(c));
   }
+  if (!x_out) return KDLAE_OK;
   TRY(stage_bwd(c, "refinement", dref));
+  if (!h.stage_dx("refinement")) return KDLAE_OK;
   TRY(stage_bwd(c, "decoder_level1", dref));  // dref now holds d(cat1) = [d up2_1 | d enc1]
-  float* de1 = c.alloc(P1 * d);
-  LAUNCH(tr::launch_copy_cols(dref + d, 2 * d, de1, d, d, P1, 0, c.s));
+  if (!h.stage_dx("decoder_level1")) return KDLAE_OK;
+  float* de1 = nullptr;
+  if (h.need_dx("down1_2.body.0")) {  // d(enc1)
+    de1 = c.alloc(P1 * d);
+    LAUNCH(tr::launch_copy_cols(dref + d, 2 * d, de1, d, d, P1, 0, c.s));
+  }
   float* du21 = c.alloc(P2 * 4 * d);
   LAUNCH(tr::launch_shuffle(dref, 2 * d, du21, 4 * d, d, B, H2, W2, 0, c.s));
-  float* ddec2 = c.alloc(P2 * 2 * d);
+  const bool x_u21 = h.need_dx("up2_1.body.0");
+  float* ddec2 = x_u21 ? c.alloc(P2 * 2 * d) : nullptr;
   TRY(conv3_bwd(c, "up2_1.body.0", {s.dec2, 2 * d}, {du21, 4 * d}, 2 * d, 4 * d, B, H2, W2, 1, {ddec2, 2 * d}));
   TRY(mark(c));
+  if (!x_u21) return KDLAE_OK;
   TRY(stage_bwd(c, "decoder_level2", ddec2));
-  float* dcat2 = c.alloc(P2 * 4 * d);
+  if (!h.stage_dx("decoder_level2")) return KDLAE_OK;
+  const bool x_r2 = h.need_dx("reduce_chan_level2");
+  float* dcat2 = x_r2 ? c.alloc(P2 * 4 * d) : nullptr;
   TRY(conv1_bwd(c, "reduce_chan_level2", {s.cat2, 4 * d}, {ddec2, 2 * d}, 4 * d, 2 * d, P2, {dcat2, 4 * d}));
   TRY(mark(c));
-  float* de2 = c.alloc(P2 * 2 * d);
-  LAUNCH(tr::launch_copy_cols(dcat2 + 2 * d, 4 * d, de2, 2 * d, 2 * d, P2, 0, c.s));
+  if (!x_r2) return KDLAE_OK;
+  float* de2 = nullptr;
+  if (h.need_dx("down2_3.body.0")) {  // d(enc2)
+    de2 = c.alloc(P2 * 2 * d);
+    LAUNCH(tr::launch_copy_cols(dcat2 + 2 * d, 4 * d, de2, 2 * d, 2 * d, P2, 0, c.s));
+  }
   float* du32 = c.alloc(P3 * 8 * d);
   LAUNCH(tr::launch_shuffle(dcat2, 4 * d, du32, 8 * d, 2 * d, B, H3, W3, 0, c.s));
-  float* ddec3 = c.alloc(P3 * 4 * d);
+  const bool x_u32 = h.need_dx("up3_2.body.0");
+  float* ddec3 = x_u32 ? c.alloc(P3 * 4 * d) : nullptr;
   TRY(conv3_bwd(c, "up3_2.body.0", {s.dec3, 4 * d}, {du32, 8 * d}, 4 * d, 8 * d, B, H3, W3, 1, {ddec3, 4 * d}));
   TRY(mark(c));
+  if (!x_u32) return KDLAE_OK;
   TRY(stage_bwd(c, "decoder_level3", ddec3));
-  float* dcat3 = c.alloc(P3 * 8 * d);
+  if (!h.stage_dx("decoder_level3")) return KDLAE_OK;
+  const bool x_r3 = h.need_dx("reduce_chan_level3");
+  float* dcat3 = x_r3 ? c.alloc(P3 * 8 * d) : nullptr;
   TRY(conv1_bwd(c, "reduce_chan_level3", {s.cat3, 8 * d}, {ddec3, 4 * d}, 8 * d, 4 * d, P3, {dcat3, 8 * d}));
   TRY(mark(c));
-  float* de3 = c.alloc(P3 * 4 * d);
-  LAUNCH(tr::launch_copy_cols(dcat3 + 4 * d, 8 * d, de3, 4 * d, 4 * d, P3, 0, c.s));
+  if (!x_r3) return KDLAE_OK;
+  float* de3 = nullptr;
+  if (h.need_dx("down3_4.body.0")) {  // d(enc3); with the frontier inside `latent` it is not formed
+    de3 = c.alloc(P3 * 4 * d);
+    LAUNCH(tr::launch_copy_cols(dcat3 + 4 * d, 8 * d, de3, 4 * d, 4 * d, P3, 0, c.s));
+  }
   float* du43 = c.alloc(P4 * 16 * d);
   LAUNCH(tr::launch_shuffle(dcat3, 8 * d, du43, 16 * d, 4 * d, B, H4, W4, 0, c.s));
-  float* dlat = c.alloc(P4 * 8 * d);
+  const bool x_u43 = h.need_dx("up4_3.body.0");
+  float* dlat = x_u43 ? c.alloc(P4 * 8 * d) : nullptr;
   TRY(conv3_bwd(c, "up4_3.body.0", {s.lat, 8 * d}, {du43, 16 * d}, 8 * d, 16 * d, B, H4, W4, 1, {dlat, 8 * d}));
   TRY(mark(c));
+  if (!x_u43) return KDLAE_OK;
   TRY(stage_bwd(c, "latent", dlat));
+  if (!h.stage_dx("latent")) return KDLAE_OK;
   // encoder, deepest first; each Downsample's dX accumulates into the skip gradient
   float* ddn3c = c.alloc(P3 * 2 * d);
   LAUNCH(tr::launch_shuffle(dlat, 8 * d, ddn3c, 2 * d, 2 * d, B, H4, W4, 1, c.s));
   TRY(conv3_bwd(c, "down3_4.body.0", {s.enc3, 4 * d}, {ddn3c, 2 * d}, 4 * d, 2 * d, B, H3, W3, 1, {de3, 4 * d}, de3,
                 4 * d));
   TRY(mark(c));
+  if (!h.need_dx("down3_4.body.0")) return KDLAE_OK;
   TRY(stage_bwd(c, "encoder_level3", de3));
+  if (!h.stage_dx("encoder_level3")) return KDLAE_OK;
   float* ddn2c = c.alloc(P2 * d);
   LAUNCH(tr::launch_shuffle(de3, 4 * d, ddn2c, d, d, B, H3, W3, 1, c.s));
   TRY(conv3_bwd(c, "down2_3.body.0", {s.enc2, 2 * d}, {ddn2c, d}, 2 * d, d, B, H2, W2, 1, {de2, 2 * d}, de2, 2 * d));
   TRY(mark(c));
+  if (!h.need_dx("down2_3.body.0")) return KDLAE_OK;
   TRY(stage_bwd(c, "encoder_level2", de2));
+  if (!h.stage_dx("encoder_level2")) return KDLAE_OK;
   float* ddn1c = c.alloc(P1 * (d / 2));
   LAUNCH(tr::launch_shuffle(de2, 2 * d, ddn1c, d / 2, d / 2, B, H2, W2, 1, c.s));
   TRY(conv3_bwd(c, "down1_2.body.0", {s.enc1, d}, {ddn1c, d / 2}, d, d / 2, B, H, W, 1, {de1, d}, de1, d));
   TRY(mark(c));
+  if (!h.need_dx("down1_2.body.0")) return KDLAE_OK;
   TRY(stage_bwd(c, "encoder_level1", de1));
+  if (!h.stage_dx("encoder_level1")) return KDLAE_OK;
   TRY(conv3_bwd(c, "patch_embed.proj", {s.img_h, ic}, {de1, d}, ic, d, B, H, W, 1, {nullptr, 0}));
   TRY(mark(c));
   return KDLAE_OK;
@@ -1108,7 +1264,70 @@ int bwd_run(kdlae_tt_handle* h, const float* theta, const float* dhq, const floa
   if (rc == KDLAE_OK) rc = flush_all(c);
   if (rc != KDLAE_OK) (void)join(c);  // leave no side launch unjoined, even on an error path
   trace_dump(h, c.s, "bwd");
+  h->bwd_launches = c.nlaunch + 1;  // + the zero fill of grad
+  h->fwd_open = false;
   return rc;
+}
+
+// The forward order of the layers (KDLAE_model.py:270-336), a chain with skip connections:
+// patch_embed, encoder_level1, ..., refinement, output, [output_param, refinement_out, output2],
+// [cen, upen, enhance, outputen].  Inside a TransformerBlock: norm1, attn.qkv, attn.qkv_dwconv,
+// attn.temperature (the softmax core), attn.project_out, norm2, ffn.project_in, ffn.dwconv,
+// ffn.project_out.
+void build_order(kdlae_tt_handle* h) {
+  const kdlae_t_config& cf = h->cfg;
+  int n = 0;
+  auto layer = [&](const std::string& l) { h->pos[l] = n++; };
+  auto stage = [&](const std::string& name, int blocks) {
+    const int lo = n;
+    for (int i = 0; i < blocks; ++i) {
+      const std::string p = name + "." + std::to_string(i);
+      for (const char* l : {".norm1.body", ".attn.qkv", ".attn.qkv_dwconv", ".attn.temperature", ".attn.project_out",
+                            ".norm2.body", ".ffn.project_in", ".ffn.dwconv", ".ffn.project_out"})
+        layer(p + l);
+    }
+    h->stage_rng[name] = {lo, n};
+  };
+  const int* nb = cf.num_blocks;
+  const int nr = cf.num_refinement_blocks;
+  layer("patch_embed.proj");
+  stage("encoder_level1", nb[0]);
+  layer("down1_2.body.0");
+  stage("encoder_level2", nb[1]);
+  layer("down2_3.body.0");
+  stage("encoder_level3", nb[2]);
+  layer("down3_4.body.0");
+  stage("latent", nb[3]);
+  layer("up4_3.body.0");
+  layer("reduce_chan_level3");
+  stage("decoder_level3", nb[2]);
+  layer("up3_2.body.0");
+  layer("reduce_chan_level2");
+  stage("decoder_level2", nb[1]);
+  layer("up2_1.body.0");
+  stage("decoder_level1", nb[0]);
+  stage("refinement", nr);
+  layer("output");
+  if (cf.params_cat) {
+    layer("output_param");
+    stage("refinement_out", nr);
+    layer("output2");
+  }
+  if (cf.static_train) {
+    layer("cen");
+    layer("upen.body.0");
+    stage("enhance", nr);
+    layer("outputen");
+  }
+}
+
+// a key's layer: the key without ".weight" / ".bias" (attn.temperature is its own layer)
+std::string layer_of(const std::string& key) {
+  for (const char* suf : {".weight", ".bias"}) {
+    const size_t n = strlen(suf);
+    if (key.size() > n && key.compare(key.size() - n, n, suf) == 0) return key.substr(0, key.size() - n);
+  }
+  return key;
 }
 
 }  // namespace
@@ -1124,6 +1343,7 @@ int kdlae_tt_create(const kdlae_t_config* cfg, int device, kdlae_tt_handle** out
   h->cfg = *cfg;
   h->device = device;
   kdlae::teacher_keys(h->cfg, h->lay);
+  build_order(h);
   *out = h;
   return KDLAE_OK;
 }
@@ -1138,6 +1358,45 @@ int kdlae_tt_param_info(const kdlae_tt_handle* h, int index, const char** name, 
 }
 
 int64_t kdlae_tt_num_floats(const kdlae_tt_handle* h) { return kdlae::train_num_floats(h); }
+
+int kdlae_tt_set_trainable(kdlae_tt_handle* h, const unsigned char* mask, int n) {
+  if (!h) return fail(KDLAE_EINVAL_CONFIG, "null argument");
+  if (h->fwd_open)
+    return fail(KDLAE_ESTATE, "kdlae_tt_set_trainable between kdlae_tt_forward and its backward: the saved "
+                              "activations were planned for the current mask");
+  const int np = h->lay.size();
+  int frontier = 0;
+  if (mask) {
+    if (n != np)
+      return fail(KDLAE_EINVAL_CONFIG, "kdlae_tt_set_trainable: mask of " + std::to_string(n) + " bytes, the model has " +
+                                           std::to_string(np) + " parameters");
+    frontier = -1;
+    for (int i = 0; i < np; ++i) {
+      if (!mask[i]) continue;
+      const int p = h->pos_of(layer_of(h->lay.names[i]));  // -1: a key the forward never touches
+      if (p >= 0 && (frontier < 0 || p < frontier)) frontier = p;
+    }
+    if (frontier < 0)
+      return fail(KDLAE_EINVAL_CONFIG, "kdlae_tt_set_trainable: the mask marks no parameter the forward uses");
+    h->mask.assign(mask, mask + np);
+  } else {
+    h->mask.clear();
+  }
+  h->frontier = frontier;
+  // the plan changed: the sizing and mark caches and the last forward's activations no longer apply
+  h->ws_B = h->ws_H = h->ws_W = -1;
+  h->ws_bytes = -1;
+  h->mk_dsr = -1;
+  h->sv.valid = false;
+  return KDLAE_OK;
+}
+
+int kdlae_tt_is_trainable(const kdlae_tt_handle* h, int index) {
+  if (!h || index < 0 || index >= h->lay.size()) return -1;
+  return (h->mask.empty() || h->mask[index]) ? 1 : 0;
+}
+
+int64_t kdlae_tt_debug_backward_launches(const kdlae_tt_handle* h) { return h ? h->bwd_launches : -1; }
 
 static int check_shape(int B, int H, int W) {
   if (B <= 0 || H <= 0 || W <= 0) return fail(KDLAE_EINVAL_SHAPE, "B, H, W must be positive");
@@ -1189,6 +1448,15 @@ int kdlae_tt_forward(kdlae_tt_handle* h, const float* theta, const float* img, c
   if (rc) return rc;
   h->sv.set(ws, B, 1, H, W);
   h->sv.fwd_end = c.off;
+  h->fwd_open = true;
+  return KDLAE_OK;
+}
+
+// the backward runs in the workspace of its forward: at least the size query's answer for that shape
+// (the backward's own peak, checked next, is not rounded to the 256-byte granule the query answers in)
+static int bwd_fits(kdlae_tt_handle* h, size_t ws_bytes) {
+  const int64_t need = kdlae_tt_workspace_bytes(h, h->sv.B, h->sv.H, h->sv.W);
+  if (need < 0 || (size_t)need > ws_bytes) return fail(KDLAE_ESTATE, "training workspace too small for the backward");
   return KDLAE_OK;
 }
 
@@ -1196,6 +1464,7 @@ int kdlae_tt_backward(kdlae_tt_handle* h, const float* theta, const float* dhq, 
                       size_t ws_bytes, void* stream) {
   if (!h || !theta || !grad || !ws) return fail(KDLAE_EINVAL_CONFIG, "null argument");
   TRY(h->sv.check(ws, "kdlae_tt_backward", "kdlae_tt_forward"));
+  TRY(bwd_fits(h, ws_bytes));
   const bool has_dsr = h->cfg.static_train && dsr;
   size_t peak = 0;  // size the backward before launching anything
   TRY(bwd_dry(h, dhq, dsr, has_dsr, grad, nullptr, &peak, nullptr));
@@ -1209,6 +1478,7 @@ int kdlae_tt_backward_marked(kdlae_tt_handle* h, const float* theta, const float
                              void* ws, size_t ws_bytes, void* stream) {
   if (!h || !theta || !grad || !ws) return fail(KDLAE_EINVAL_CONFIG, "null argument");
   TRY(h->sv.check(ws, "kdlae_tt_backward_marked", "kdlae_tt_forward"));
+  TRY(bwd_fits(h, ws_bytes));
   const bool has_dsr = h->cfg.static_train && dsr;
   const bool cached = h->mk_dsr == (int)has_dsr && h->mk_B == h->sv.B && h->mk_H == h->sv.H && h->mk_W == h->sv.W &&
                       h->mk_fwd_end == h->sv.fwd_end;

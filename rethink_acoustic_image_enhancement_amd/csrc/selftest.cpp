@@ -425,28 +425,34 @@ extern "C" int kdlae_debug_train(const kdlae_debug_train_desc* d, void* stream) 
     }
     case 4:
     case 5:
-    case 6: {
+    case 6:
+    case 16:    // ops 16-18: ops 4-6 with the weight gradient left out (the dx-only kernels); part is ignored
+    case 17:
+    case 18: {
       if (!geo || !d->w || C < 1 || C > (1 << 20)) return fail(KDLAE_EINVAL_SHAPE, bad);
-      const int Ct = d->op == 6 ? C : 2 * C;  // channels of y / dy (and of the partial rows)
-      const int nin = d->op == 4 ? 3 : 2;
+      const bool dx_only = d->op >= 16;
+      const int op = dx_only ? d->op - 12 : d->op;
+      const int Ct = op == 6 ? C : 2 * C;  // channels of y / dy (and of the partial rows)
+      const int nin = op == 4 ? 3 : (op == 6 && dx_only) ? 1 : 2;  // op 18 does not read in1
       // in0: dg (C) or dyd (Ct); the rest: yd / y (Ct)
       int ldmax = d->ldo[0];
       for (int i = 0; i < nin; ++i) {
-        if (!in_ok(i, (i == 0 && d->op != 6) ? C : Ct, px)) return fail(KDLAE_EINVAL_SHAPE, bad);
+        if (!in_ok(i, (i == 0 && op != 6) ? C : Ct, px)) return fail(KDLAE_EINVAL_SHAPE, bad);
         ldmax = std::max(ldmax, d->ldi[i]);
       }
       if (!out_ok(0, Ct, px) || !img_ok(ldmax)) return fail(KDLAE_EINVAL_SHAPE, bad);
-      if (!d->part || d->part_floats < (long long)tr::dwg_blocks(d->Bn, d->H, d->W) * 10 * Ct)
+      if (!dx_only && (!d->part || d->part_floats < (long long)tr::dwg_blocks(d->Bn, d->H, d->W) * 10 * Ct))
         return fail(KDLAE_EINVAL_SHAPE, "part must hold blocks * 10 * channels floats");
-      if (d->op == 4)
+      float* part = dx_only ? nullptr : d->part;  // a null part selects the dx-only kernel
+      if (op == 4)
         e = tr::launch_dwgate_bwd(d->in[0], d->ldi[0], d->in[1], d->ldi[1], d->in[2], d->ldi[2], d->w, C, d->Bn, d->H,
-                                  d->W, d->out[0], d->ldo[0], d->part, s);
-      else if (d->op == 5)
+                                  d->W, d->out[0], d->ldo[0], part, s);
+      else if (op == 5)
         e = tr::launch_dwgate_bwd_rc(d->in[0], d->ldi[0], d->in[1], d->ldi[1], d->w, d->bias, C, d->Bn, d->H, d->W,
-                                     d->out[0], d->ldo[0], d->part, s);
+                                     d->out[0], d->ldo[0], part, s);
       else
-        e = tr::launch_dw_bwd(d->in[0], d->ldi[0], d->in[1], d->ldi[1], d->w, C, d->Bn, d->H, d->W, d->out[0],
-                              d->ldo[0], d->part, s);
+        e = tr::launch_dw_bwd(d->in[0], d->ldi[0], dx_only ? nullptr : d->in[1], dx_only ? 0 : d->ldi[1], d->w, C, d->Bn,
+                              d->H, d->W, d->out[0], d->ldo[0], part, s);
       break;
     }
     case 7: {
@@ -527,7 +533,16 @@ extern "C" int kdlae_debug_train(const kdlae_debug_train_desc* d, void* stream) 
       e = tr::launch_pack_w3(d->w, C, d->C2, d->flag, d->out[0], s);
       break;
     }
-    default: return fail(KDLAE_EINVAL_CONFIG, "op must be 0..15");
+    case 19: {  // LayerNorm backward, dx only: in0 = dy, in1 = x, in2 = stats [P][2], in3 = R (or null), w
+      if (C < 1 || C > 512 || d->P < 1 || d->P >= kMaxIdx || !d->w || !d->in[2] || !in_ok(0, C, d->P) ||
+          !in_ok(1, C, d->P) || (d->in[3] && !in_ok(3, C, d->P)) || !out_ok(0, C, d->P))
+        return fail(KDLAE_EINVAL_SHAPE, bad);
+      const int nblk = d->nblk >= 1 ? d->nblk : 1;
+      e = tr::launch_ln_bwd(d->in[0], d->ldi[0], d->in[1], d->ldi[1], d->w, d->in[2], C, d->P, d->flag & 1, d->in[3],
+                            d->in[3] ? d->ldi[3] : 0, d->out[0], d->ldo[0], nullptr, nblk, s, (d->flag & 2) != 0);
+      break;
+    }
+    default: return fail(KDLAE_EINVAL_CONFIG, "op must be 0..19");
   }
   if (e != hipSuccess) return fail(KDLAE_EHIP, std::string("kdlae_debug_train: ") + hipGetErrorString(e));
   return KDLAE_OK;

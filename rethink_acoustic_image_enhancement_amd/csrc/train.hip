@@ -667,18 +667,20 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
   }
 }
 
-template <int V>
+// DW = false (ln_bwd_kernel and ln2_bwd_kernel): dx alone (weight and bias frozen): no per-block
+// weight / bias partials, no LDS, no barrier; `part` is not written.  dx has the DW = true kernel's bits.
+template <int V, bool DW>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ dy, int ldd, const float* __restrict__ x,
                                                      int ldx, const float* __restrict__ w,
                                                      const float* __restrict__ stats, int C, long long P, int biasfree,
                                                      const float* R, int ldr, float* dx, int lddx,
                                                      float* __restrict__ part) {
-  __shared__ float red[4][2 * 64 * V];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  float aw[V], ab[V], wr[V];
+  [[maybe_unused]] float aw[V], ab[V];
+  float wr[V];
 #pragma unroll
   for (int i = 0; i < V; ++i) {
-    aw[i] = ab[i] = 0.f;
+    if constexpr (DW) aw[i] = ab[i] = 0.f;
     const int c = lane + 64 * i;
     wr[i] = c < C ? w[c] : 0.f;
   }
@@ -707,8 +709,10 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
 #pragma unroll
       for (int i = 0; i < V; ++i) {
         const float xh = biasfree ? xv[q][i] * r[q] : (xv[q][i] - mu[q]) * r[q];
-        aw[i] += dv[q][i] * xh;
-        ab[i] += dv[q][i];
+        if constexpr (DW) {
+          aw[i] += dv[q][i] * xh;
+          ab[i] += dv[q][i];
+        }
         gv[i] = dv[q][i] * wr[i];
         s1 += gv[i] * (biasfree ? xv[q][i] : xh);
         s2 += gv[i];
@@ -728,19 +732,29 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
       }
     }
   }
+  if constexpr (DW) {
+    __shared__ float red[4][2 * 64 * V];
 #pragma unroll
-  for (int i = 0; i < V; ++i) {
-    red[wv][64 * i + lane] = aw[i];
-    red[wv][64 * V + 64 * i + lane] = ab[i];
-  }
-  __syncthreads();
-  const int ncol = biasfree ? C : 2 * C;
-  for (int c = threadIdx.x; c < ncol; c += blockDim.x) {
-    const int off = c < C ? c : 64 * V + (c - C);
-    part[(long long)blockIdx.x * ncol + c] = ((red[0][off] + red[1][off]) + red[2][off]) + red[3][off];
+    for (int i = 0; i < V; ++i) {
+      red[wv][64 * i + lane] = aw[i];
+      red[wv][64 * V + 64 * i + lane] = ab[i];
+    }
+    __syncthreads();
+    const int ncol = biasfree ? C : 2 * C;
+    for (int c = threadIdx.x; c < ncol; c += blockDim.x) {
+      const int off = c < C ? c : 64 * V + (c - C);
+      part[(long long)blockIdx.x * ncol + c] = ((red[0][off] + red[1][off]) + red[2][off]) + red[3][off];
+    }
   }
 }
 
+#define LN_DISPATCH_DW(KERNEL, DW, grid, ...)                                                     \
+  do {                                                                                            \
+    if (C <= 64) hipLaunchKernelGGL((KERNEL<1, DW>), grid, dim3(256), 0, s, __VA_ARGS__);           \
+    else if (C <= 128) hipLaunchKernelGGL((KERNEL<2, DW>), grid, dim3(256), 0, s, __VA_ARGS__);     \
+    else if (C <= 256) hipLaunchKernelGGL((KERNEL<4, DW>), grid, dim3(256), 0, s, __VA_ARGS__);     \
+    else hipLaunchKernelGGL((KERNEL<8, DW>), grid, dim3(256), 0, s, __VA_ARGS__);                   \
+  } while (0)
 #define LN_DISPATCH(KERNEL, grid, ...)                                                           \
   do {                                                                                            \
     if (C <= 64) hipLaunchKernelGGL((KERNEL<1>), grid, dim3(256), 0, s, __VA_ARGS__);               \
@@ -815,22 +829,22 @@ __global__ __launch_bounds__(256) void ln2_fwd_kernel(const float* __restrict__ 
   }
 }
 
-template <int G, int NV>
+template <int G, int NV, bool DW>
 __global__ __launch_bounds__(256) void ln2_bwd_kernel(const float* __restrict__ dy, int ldd, const float* __restrict__ x,
                                                       int ldx, const float* __restrict__ w,
                                                       const float* __restrict__ stats, int C, long long P, int biasfree,
                                                       const float* R, int ldr, float* dx, int lddx,
                                                       float* __restrict__ part) {
   constexpr int PPW = 64 / G;
-  __shared__ f32x4 red[4][2][G * NV];
   const int lane = threadIdx.x & 63, wv_ = threadIdx.x >> 6, gl = lane % G, gp = lane / G;
   const int Cq = C >> 2;
-  f32x4 wr[NV], aw[NV], ab[NV];
+  f32x4 wr[NV];
+  [[maybe_unused]] f32x4 aw[NV], ab[NV];
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
     const int q = gl + G * j;
     wr[j] = q < Cq ? *reinterpret_cast<const f32x4*>(w + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
-    aw[j] = ab[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (DW) aw[j] = ab[j] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   const long long nwave = (long long)gridDim.x * 4;
   const float invC = 1.f / C;
@@ -854,8 +868,10 @@ __global__ __launch_bounds__(256) void ln2_bwd_kernel(const float* __restrict__ 
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float xh = biasfree ? xv[j][e] * r : (xv[j][e] - mu) * r;
-        aw[j][e] += dv[j][e] * xh;
-        ab[j][e] += dv[j][e];
+        if constexpr (DW) {
+          aw[j][e] += dv[j][e] * xh;
+          ab[j][e] += dv[j][e];
+        }
         gv[j][e] = dv[j][e] * wr[j][e];
         s1 += gv[j][e] * (biasfree ? xv[j][e] : xh);
         s2 += gv[j][e];
@@ -877,30 +893,33 @@ __global__ __launch_bounds__(256) void ln2_bwd_kernel(const float* __restrict__ 
       *reinterpret_cast<f32x4*>(dx + p * lddx + 4 * q) = o;
     }
   }
-  // per-channel partials: the PPW pixel groups of a wave (lanes gl, gl + G, ...) in fixed order,
-  // then the 4 waves in fixed order
+  if constexpr (DW) {
+    // per-channel partials: the PPW pixel groups of a wave (lanes gl, gl + G, ...) in fixed order,
+    // then the 4 waves in fixed order
+    __shared__ f32x4 red[4][2][G * NV];
 #pragma unroll
-  for (int j = 0; j < NV; ++j)
+    for (int j = 0; j < NV; ++j)
 #pragma unroll
-    for (int e = 0; e < 4; ++e)
+      for (int e = 0; e < 4; ++e)
 #pragma unroll
-      for (int o = G; o < 64; o <<= 1) {
-        aw[j][e] += __shfl_xor(aw[j][e], o);
-        ab[j][e] += __shfl_xor(ab[j][e], o);
+        for (int o = G; o < 64; o <<= 1) {
+          aw[j][e] += __shfl_xor(aw[j][e], o);
+          ab[j][e] += __shfl_xor(ab[j][e], o);
+        }
+    if (gp == 0)
+#pragma unroll
+      for (int j = 0; j < NV; ++j) {
+        red[wv_][0][gl + G * j] = aw[j];
+        red[wv_][1][gl + G * j] = ab[j];
       }
-  if (gp == 0)
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-      red[wv_][0][gl + G * j] = aw[j];
-      red[wv_][1][gl + G * j] = ab[j];
+    __syncthreads();
+    const int ncol = biasfree ? C : 2 * C;
+    for (int c = threadIdx.x; c < ncol; c += blockDim.x) {
+      const int which = c < C ? 0 : 1, cc = c < C ? c : c - C;
+      const int q = cc >> 2, e = cc & 3;
+      part[(long long)blockIdx.x * ncol + c] =
+          ((red[0][which][q][e] + red[1][which][q][e]) + red[2][which][q][e]) + red[3][which][q][e];
     }
-  __syncthreads();
-  const int ncol = biasfree ? C : 2 * C;
-  for (int c = threadIdx.x; c < ncol; c += blockDim.x) {
-    const int which = c < C ? 0 : 1, cc = c < C ? c : c - C;
-    const int q = cc >> 2, e = cc & 3;
-    part[(long long)blockIdx.x * ncol + c] =
-        ((red[0][which][q][e] + red[1][which][q][e]) + red[2][which][q][e]) + red[3][which][q][e];
   }
 }
 
@@ -908,6 +927,13 @@ static inline bool ln2_ok(const void* a, int lda, const void* b, int ldb, int C)
   return C % 4 == 0 && C <= 512 && ((uintptr_t)a & 15) == 0 && ((uintptr_t)b & 15) == 0 && lda % 4 == 0 && ldb % 4 == 0;
 }
 
+#define LN2_DISPATCH_DW(KERNEL, DW, grid, ...)                                                       \
+  do {                                                                                               \
+    if (C <= 64) hipLaunchKernelGGL((KERNEL<16, 1, DW>), grid, dim3(256), 0, s, __VA_ARGS__);          \
+    else if (C <= 128) hipLaunchKernelGGL((KERNEL<32, 1, DW>), grid, dim3(256), 0, s, __VA_ARGS__);    \
+    else if (C <= 256) hipLaunchKernelGGL((KERNEL<64, 1, DW>), grid, dim3(256), 0, s, __VA_ARGS__);    \
+    else hipLaunchKernelGGL((KERNEL<64, 2, DW>), grid, dim3(256), 0, s, __VA_ARGS__);                  \
+  } while (0)
 #define LN2_DISPATCH(KERNEL, grid, ...)                                                              \
   do {                                                                                               \
     if (C <= 64) hipLaunchKernelGGL((KERNEL<16, 1>), grid, dim3(256), 0, s, __VA_ARGS__);              \
@@ -933,10 +959,13 @@ hipError_t launch_ln_bwd(const float* dy, int ldd, const float* x, int ldx, cons
                          hipStream_t s, bool generic) {
   if (C > 512) return hipErrorInvalidValue;
   if (!generic && ln2_ok(dy, ldd, x, ldx, C) && ln2_ok(dx, lddx, w, 4, C) && (!R || ln2_ok(R, ldr, R, ldr, C))) {
-    LN2_DISPATCH(ln2_bwd_kernel, dim3(nblk), dy, ldd, x, ldx, w, stats, C, P, biasfree, R, ldr, dx, lddx, part);
+    // part == null: the dx-only kernels (the norm's weight and bias are frozen)
+    if (part) LN2_DISPATCH_DW(ln2_bwd_kernel, true, dim3(nblk), dy, ldd, x, ldx, w, stats, C, P, biasfree, R, ldr, dx, lddx, part);
+    else LN2_DISPATCH_DW(ln2_bwd_kernel, false, dim3(nblk), dy, ldd, x, ldx, w, stats, C, P, biasfree, R, ldr, dx, lddx, part);
     return hipGetLastError();
   }
-  LN_DISPATCH(ln_bwd_kernel, dim3(nblk), dy, ldd, x, ldx, w, stats, C, P, biasfree, R, ldr, dx, lddx, part);
+  if (part) LN_DISPATCH_DW(ln_bwd_kernel, true, dim3(nblk), dy, ldd, x, ldx, w, stats, C, P, biasfree, R, ldr, dx, lddx, part);
+  else LN_DISPATCH_DW(ln_bwd_kernel, false, dim3(nblk), dy, ldd, x, ldx, w, stats, C, P, biasfree, R, ldr, dx, lddx, part);
   return hipGetLastError();
 }
 

@@ -196,7 +196,10 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 template <bool GATE> struct DwType { using T = float; };
 template <> struct DwType<true> { using T = f2; };
 
-template <bool GATE>
+// DW = false: the input gradient alone (the layer's weight and bias are frozen): no accumulators, no
+// layer-input rows (yin is not read; null is fine), no LDS, no barrier, no partial stores.  dy is
+// the same arithmetic in the same order, so it has the bits of the DW = true kernel's.
+template <bool GATE, bool DW>
 __global__ __launch_bounds__(256) void dw_bwd_kernel(const float* __restrict__ dg, int ldg,
                                                      const float* __restrict__ yd, int ldyd,
                                                      const float* __restrict__ yin, int ldi,
@@ -205,7 +208,6 @@ __global__ __launch_bounds__(256) void dw_bwd_kernel(const float* __restrict__ d
                                                      float* __restrict__ part) {
   using T = typename DwType<GATE>::T;
   constexpr int NH = GATE ? 2 : 1;
-  __shared__ float red[4][64][10 * NH];
   const Geo o = geo(hid, H, W, tiles_x, ty);
   const int c = o.c;
   auto comp = [](const T& v, int h) -> float {
@@ -221,20 +223,26 @@ __global__ __launch_bounds__(256) void dw_bwd_kernel(const float* __restrict__ d
 #pragma unroll
   for (int t = 0; t < 9; ++t)
     wf[t] = pack(o.live ? w[c * 9 + 8 - t] : 0.f, (GATE && o.live) ? w[(hid + c) * 9 + 8 - t] : 0.f);
-  T acc[10];
+  [[maybe_unused]] T acc[DW ? 10 : 1];
+  if constexpr (DW) {
 #pragma unroll
-  for (int t = 0; t < 10; ++t) acc[t] = pack(0.f, 0.f);
-  T d[3][kU + 2], x[3][kU + 2];
+    for (int t = 0; t < 10; ++t) acc[t] = pack(0.f, 0.f);
+  }
+  T d[3][kU + 2];
+  [[maybe_unused]] T x[DW ? 3 : 1][kU + 2];
   // raw inputs of one row (GATE: dg, yd1, yd2; else dyd in r1) and the layer input rows
-  float rg[GATE ? kU + 2 : 1], r1[kU + 2], r2[GATE ? kU + 2 : 1], rx[NH][kU + 2];
+  float rg[GATE ? kU + 2 : 1], r1[kU + 2], r2[GATE ? kU + 2 : 1];
+  [[maybe_unused]] float rx[DW ? NH : 1][kU + 2];
   auto load_raw = [&](int yy) {
     if constexpr (GATE) {
       load_row(dg, ldg, o, H, W, yy, c, rg);
       load_row(yd, ldyd, o, H, W, yy, hid + c, r2);
     }
     load_row(yd, ldyd, o, H, W, yy, c, r1);
+    if constexpr (DW) {
 #pragma unroll
-    for (int h = 0; h < NH; ++h) load_row(yin, ldi, o, H, W, yy, h * hid + c, rx[h]);
+      for (int h = 0; h < NH; ++h) load_row(yin, ldi, o, H, W, yy, h * hid + c, rx[h]);
+    }
   };
   // dyd of the raw row for both halves: gate backward of (dg, yd1, yd2), or the given gradient
   auto row_d = [&](T (&dd)[kU + 2]) {
@@ -250,9 +258,11 @@ __global__ __launch_bounds__(256) void dw_bwd_kernel(const float* __restrict__ d
       }
     }
   };
-  auto take_x = [&](int slot) {
+  auto take_x = [&]([[maybe_unused]] int slot) {
+    if constexpr (DW) {
 #pragma unroll
-    for (int j = 0; j < kU + 2; ++j) x[slot][j] = pack(rx[0][j], rx[NH - 1][j]);
+      for (int j = 0; j < kU + 2; ++j) x[slot][j] = pack(rx[0][j], rx[NH - 1][j]);
+    }
   };
   load_raw(o.y0 - 1);
   row_d(d[0]);
@@ -279,41 +289,49 @@ __global__ __launch_bounds__(256) void dw_bwd_kernel(const float* __restrict__ d
 #pragma unroll
         for (int h = 0; h < NH; ++h) st_img(rdy, col_off(o, xx, W, lddy, h * hid + c) + ro, comp(s, h));
       }
-      // weight / bias gradient: centre dyd times the input at each tap (zero past the image)
-      const T dc = d[1][u + 1];
+      if constexpr (DW) {
+        // weight / bias gradient: centre dyd times the input at each tap (zero past the image)
+        const T dc = d[1][u + 1];
 #pragma unroll
-      for (int ty = 0; ty < 3; ++ty)
+        for (int ty = 0; ty < 3; ++ty)
 #pragma unroll
-        for (int tx = 0; tx < 3; ++tx) acc[ty * 3 + tx] = __builtin_elementwise_fma(dc, x[ty][u + tx], acc[ty * 3 + tx]);
-      acc[9] += dc;
+          for (int tx = 0; tx < 3; ++tx)
+            acc[ty * 3 + tx] = __builtin_elementwise_fma(dc, x[ty][u + tx], acc[ty * 3 + tx]);
+        acc[9] += dc;
+      }
     }
 #pragma unroll
     for (int j = 0; j < kU + 2; ++j) {
       d[0][j] = d[1][j];
       d[1][j] = d[2][j];
-      x[0][j] = x[1][j];
-      x[1][j] = x[2][j];
+      if constexpr (DW) {
+        x[0][j] = x[1][j];
+        x[1][j] = x[2][j];
+      }
     }
   }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if constexpr (DW) {
+    __shared__ float red[4][64][10 * NH];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
-  for (int h = 0; h < NH; ++h)
+    for (int h = 0; h < NH; ++h)
 #pragma unroll
-    for (int t = 0; t < 10; ++t) red[wv][lane][h * 10 + t] = comp(acc[t], h);
-  __syncthreads();
-  if (wv != 0 || !o.live) return;
-  const int Ctot = NH * hid;
-  float* pr = part + ((long long)o.b * gridDim.x + blockIdx.x) * 10 * Ctot;
+      for (int t = 0; t < 10; ++t) red[wv][lane][h * 10 + t] = comp(acc[t], h);
+    __syncthreads();
+    if (wv != 0 || !o.live) return;
+    const int Ctot = NH * hid;
+    float* pr = part + ((long long)o.b * gridDim.x + blockIdx.x) * 10 * Ctot;
 #pragma unroll
-  for (int h = 0; h < NH; ++h)
+    for (int h = 0; h < NH; ++h)
 #pragma unroll
-    for (int t = 0; t < 10; ++t) {
-      const float s = ((red[0][lane][h * 10 + t] + red[1][lane][h * 10 + t]) + red[2][lane][h * 10 + t]) +
-                      red[3][lane][h * 10 + t];
-      const int ch = h * hid + c;
-      if (t < 9) pr[ch * 9 + t] = s;
-      else pr[9 * Ctot + ch] = s;
-    }
+      for (int t = 0; t < 10; ++t) {
+        const float s = ((red[0][lane][h * 10 + t] + red[1][lane][h * 10 + t]) + red[2][lane][h * 10 + t]) +
+                        red[3][lane][h * 10 + t];
+        const int ch = h * hid + c;
+        if (t < 9) pr[ch * 9 + t] = s;
+        else pr[9 * Ctot + ch] = s;
+      }
+  }
 }
 
 // The GDFN backward without a stored yd: yd = dw(y) (+ bias) is recomputed from the layer input y,
@@ -324,6 +342,8 @@ __global__ __launch_bounds__(256) void dw_bwd_kernel(const float* __restrict__ d
 // A thread walks its kU columns down the rows with a 4-row x (kU + 4)-column window of y (both
 // halves packed as one float2) and a 3-row x (kU + 2)-column window of dyd: output row yy needs dyd
 // rows yy - 1 .. yy + 1, dyd row r needs yd row r, and yd row r needs y rows r - 1 .. r + 1.
+// DW = false: dy alone (it still reads y, from which yd is rebuilt); same dy bits.
+template <bool DW>
 __global__ __launch_bounds__(256) void dwgate_bwd_rc_kernel(const float* __restrict__ dg, int ldg,
                                                             const float* __restrict__ yin, int ldi,
                                                             const float* __restrict__ w,
@@ -331,16 +351,17 @@ __global__ __launch_bounds__(256) void dwgate_bwd_rc_kernel(const float* __restr
                                                             int tiles_x, int ty, float* __restrict__ dy, int lddy,
                                                             float* __restrict__ part) {
   constexpr int NY = kU + 4, ND = kU + 2;
-  __shared__ float red[4][64][20];
   const Geo o = geo(hid, H, W, tiles_x, ty);
   const int c = o.c;
   f2 wv[9];  // forward taps; the transposed conv reads them flipped
 #pragma unroll
   for (int t = 0; t < 9; ++t) wv[t] = o.live ? f2{w[c * 9 + t], w[(hid + c) * 9 + t]} : f2{0.f, 0.f};
   const f2 bv = (o.live && bias) ? f2{bias[c], bias[hid + c]} : f2{0.f, 0.f};
-  f2 acc[10];
+  [[maybe_unused]] f2 acc[DW ? 10 : 1];
+  if constexpr (DW) {
 #pragma unroll
-  for (int t = 0; t < 10; ++t) acc[t] = f2{0.f, 0.f};
+    for (int t = 0; t < 10; ++t) acc[t] = f2{0.f, 0.f};
+  }
   // y row yy, columns x0 - 2 .. x0 + kU + 1 (zero outside the image / past the channels)
   const __amdgpu_buffer_rsrc_t ryin = img_rsrc(yin, ldi, o, H, W), rdy = img_rsrc(dy, lddy, o, H, W);
   auto load_y = [&](int yy, f2 (&r)[NY]) {
@@ -401,13 +422,16 @@ __global__ __launch_bounds__(256) void dwgate_bwd_rc_kernel(const float* __restr
         st_img(rdy, col_off(o, xx, W, lddy, c) + ro, s.x);
         st_img(rdy, col_off(o, xx, W, lddy, hid + c) + ro, s.y);
       }
-      // weight / bias gradient: centre dyd times the input at each tap (y at column x0 + u + tx - 1)
-      const f2 dc = D[1][u + 1];
+      if constexpr (DW) {
+        // weight / bias gradient: centre dyd times the input at each tap (y at column x0 + u + tx - 1)
+        const f2 dc = D[1][u + 1];
 #pragma unroll
-      for (int ty2 = 0; ty2 < 3; ++ty2)
+        for (int ty2 = 0; ty2 < 3; ++ty2)
 #pragma unroll
-        for (int tx = 0; tx < 3; ++tx) acc[ty2 * 3 + tx] = __builtin_elementwise_fma(dc, Y[ty2][u + tx + 1], acc[ty2 * 3 + tx]);
-      acc[9] += dc;
+          for (int tx = 0; tx < 3; ++tx)
+            acc[ty2 * 3 + tx] = __builtin_elementwise_fma(dc, Y[ty2][u + tx + 1], acc[ty2 * 3 + tx]);
+        acc[9] += dc;
+      }
     }
     if (yy + 1 >= o.y1) break;
 #pragma unroll
@@ -426,26 +450,29 @@ __global__ __launch_bounds__(256) void dwgate_bwd_rc_kernel(const float* __restr
     load_y(yy + 4, y4);
     load_row(dg, ldg, o, H, W, yy + 3, c, rg);
   }
-  const int lane = threadIdx.x & 63, wv_ = threadIdx.x >> 6;
-#pragma unroll
-  for (int t = 0; t < 10; ++t) {
-    red[wv_][lane][t] = acc[t].x;
-    red[wv_][lane][10 + t] = acc[t].y;
-  }
-  __syncthreads();
-  if (wv_ != 0 || !o.live) return;
-  const int Ctot = 2 * hid;
-  float* pr = part + ((long long)o.b * gridDim.x + blockIdx.x) * 10 * Ctot;
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
+  if constexpr (DW) {
+    __shared__ float red[4][64][20];
+    const int lane = threadIdx.x & 63, wv_ = threadIdx.x >> 6;
 #pragma unroll
     for (int t = 0; t < 10; ++t) {
-      const float s = ((red[0][lane][h * 10 + t] + red[1][lane][h * 10 + t]) + red[2][lane][h * 10 + t]) +
-                      red[3][lane][h * 10 + t];
-      const int ch = h * hid + c;
-      if (t < 9) pr[ch * 9 + t] = s;
-      else pr[9 * Ctot + ch] = s;
+      red[wv_][lane][t] = acc[t].x;
+      red[wv_][lane][10 + t] = acc[t].y;
     }
+    __syncthreads();
+    if (wv_ != 0 || !o.live) return;
+    const int Ctot = 2 * hid;
+    float* pr = part + ((long long)o.b * gridDim.x + blockIdx.x) * 10 * Ctot;
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int t = 0; t < 10; ++t) {
+        const float s = ((red[0][lane][h * 10 + t] + red[1][lane][h * 10 + t]) + red[2][lane][h * 10 + t]) +
+                        red[3][lane][h * 10 + t];
+        const int ch = h * hid + c;
+        if (t < 9) pr[ch * 9 + t] = s;
+        else pr[9 * Ctot + ch] = s;
+      }
+  }
 }
 
 }  // namespace
@@ -469,8 +496,13 @@ hipError_t launch_dwgate_bwd(const float* dg, int ldg, const float* yd, int ldyd
                              hipStream_t s) {
   if (!img_bytes_ok(H, W, std::max(std::max(ldg, ldyd), std::max(ldi, lddy)))) return hipErrorInvalidValue;
   const int ty = rows_per_block(Bn, H, W), tx = (W + kTX - 1) / kTX, nty = (H + ty - 1) / ty;
-  hipLaunchKernelGGL(dw_bwd_kernel<true>, dim3(tx * nty, (hid + 63) / 64, Bn), dim3(256), 0, s, dg, ldg, yd, ldyd,
-                     yin, ldi, w, hid, H, W, tx, ty, dy, lddy, part);
+  const dim3 grid(tx * nty, (hid + 63) / 64, Bn);
+  if (part)
+    hipLaunchKernelGGL((dw_bwd_kernel<true, true>), grid, dim3(256), 0, s, dg, ldg, yd, ldyd, yin, ldi, w, hid, H, W,
+                       tx, ty, dy, lddy, part);
+  else  // part == null: the input gradient alone (yin is not read)
+    hipLaunchKernelGGL((dw_bwd_kernel<true, false>), grid, dim3(256), 0, s, dg, ldg, yd, ldyd, yin, ldi, w, hid, H, W,
+                       tx, ty, dy, lddy, part);
   return hipGetLastError();
 }
 
@@ -478,17 +510,27 @@ hipError_t launch_dwgate_bwd_rc(const float* dg, int ldg, const float* yin, int 
                                 int hid, int Bn, int H, int W, float* dy, int lddy, float* part, hipStream_t s) {
   if (!img_bytes_ok(H, W, std::max(ldg, std::max(ldi, lddy)))) return hipErrorInvalidValue;
   const int ty = rows_per_block(Bn, H, W), tx = (W + kTX - 1) / kTX, nty = (H + ty - 1) / ty;
-  hipLaunchKernelGGL(dwgate_bwd_rc_kernel, dim3(tx * nty, (hid + 63) / 64, Bn), dim3(256), 0, s, dg, ldg, yin, ldi, w, b,
-                     hid, H, W, tx, ty, dy, lddy, part);
+  const dim3 grid(tx * nty, (hid + 63) / 64, Bn);
+  if (part)
+    hipLaunchKernelGGL(dwgate_bwd_rc_kernel<true>, grid, dim3(256), 0, s, dg, ldg, yin, ldi, w, b, hid, H, W, tx, ty,
+                       dy, lddy, part);
+  else  // part == null: the input gradient alone
+    hipLaunchKernelGGL(dwgate_bwd_rc_kernel<false>, grid, dim3(256), 0, s, dg, ldg, yin, ldi, w, b, hid, H, W, tx, ty,
+                       dy, lddy, part);
   return hipGetLastError();
 }
 
 hipError_t launch_dw_bwd(const float* dyd, int ldd, const float* yin, int ldi, const float* w, int C, int Bn, int H,
                          int W, float* dy, int lddy, float* part, hipStream_t s) {
-  if (!img_bytes_ok(H, W, std::max(ldd, std::max(ldi, lddy)))) return hipErrorInvalidValue;
+  if (!img_bytes_ok(H, W, std::max(ldd, std::max(part ? ldi : 0, lddy)))) return hipErrorInvalidValue;
   const int ty = rows_per_block(Bn, H, W), tx = (W + kTX - 1) / kTX, nty = (H + ty - 1) / ty;
-  hipLaunchKernelGGL(dw_bwd_kernel<false>, dim3(tx * nty, (C + 63) / 64, Bn), dim3(256), 0, s, nullptr, 0, dyd, ldd,
-                     yin, ldi, w, C, H, W, tx, ty, dy, lddy, part);
+  const dim3 grid(tx * nty, (C + 63) / 64, Bn);
+  if (part)
+    hipLaunchKernelGGL((dw_bwd_kernel<false, true>), grid, dim3(256), 0, s, nullptr, 0, dyd, ldd, yin, ldi, w, C, H, W,
+                       tx, ty, dy, lddy, part);
+  else  // part == null: the input gradient alone; yin (the weight gradient's operand) may be null
+    hipLaunchKernelGGL((dw_bwd_kernel<false, false>), grid, dim3(256), 0, s, nullptr, 0, dyd, ldd, nullptr, 0, w, C, H,
+                       W, tx, ty, dy, lddy, part);
   return hipGetLastError();
 }
 

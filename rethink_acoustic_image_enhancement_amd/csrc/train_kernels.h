@@ -88,6 +88,10 @@ hipError_t launch_dwgate_bwd(const float* dg, int ldg, const float* yd, int ldyd
 // launch_dwgate_bwd given the stored yd); the forward then passes yd = null to launch_dwgate_fwd.
 hipError_t launch_dwgate_bwd_rc(const float* dg, int ldg, const float* yin, int ldi, const float* w, const float* b,
                                 int hid, int Bn, int H, int W, float* dy, int lddy, float* part, hipStream_t s);
+// part == null in the three backward launchers above and below (and in launch_ln_bwd): the layer's
+// weight and bias are frozen, so the dx-only variant of the kernel runs (template flag DW = false: no
+// accumulators, LDS, barrier or partial stores; the same dx / dy bits).  launch_dw_bwd then does not
+// read yin, which may be null.
 hipError_t launch_dw_bwd(const float* dyd, int ldd, const float* yin, int ldi, const float* w, int C, int Bn, int H,
                          int W, float* dy, int lddy, float* part, hipStream_t s);
 

@@ -29,7 +29,8 @@ from . import _lib
 __all__ = ["TrainEngine", "TeacherTrainFn", "L1LossSr", "KDLAETrainer", "MixingAugment", "sync_gradients",
            "grad_buckets", "sync_gradients_bucketed", "StudentTrainEngine", "StudentTrainFn",
            "L1LossForVideoFrames", "KDLAESTrainer", "AsdqeTrainEngine", "AsdqeTrainFn", "asdqe_train_forward",
-           "asdqe_dropout_masks", "ASDQETrainer", "flat_to_optim_state", "optim_state_to_flat"]
+           "asdqe_dropout_masks", "ASDQETrainer", "flat_to_optim_state", "optim_state_to_flat",
+           "freeze_except_patch_embed_and_enhance"]
 
 
 def _vp(t):
@@ -120,13 +121,22 @@ class _TrainingState:
         return dict(lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay,
                     optimizer=self._optimizer_name)
 
+    def _state_keys(self):
+        """The engine's ``(name, numel, offset)`` entries the optimizer holds: the parameters with
+        ``requires_grad``, in ``named_parameters()`` order (what ImageCleanModel.setup_optimizers hands to
+        AdamW, image_restoration_model.py:139-160); all of them for an engine without a trainable mask."""
+        tr = getattr(self.engine, "trainable", None)
+        return list(self.engine.keys) if tr is None else [k for k, t in zip(self.engine.keys, tr) if t]
+
     def _shapes(self):
-        return [tuple(p.shape) for p in self.model.parameters()]
+        tr = getattr(self.engine, "trainable", None)
+        shapes = [tuple(p.shape) for p in self.model.parameters()]
+        return shapes if tr is None else [sh for sh, t in zip(shapes, tr) if t]
 
     def training_state(self, epoch: int, current_iter: int) -> dict:
         """The dict ``torch.save`` writes as ``{current_iter}.state``.  Call it after iteration
         ``current_iter``'s ``optimize_parameters``; it copies the moments (later steps do not change it)."""
-        opt = flat_to_optim_state(self.engine.keys, self.exp_avg, self.exp_avg_sq, self.step_count, self._hyper(),
+        opt = flat_to_optim_state(self._state_keys(), self.exp_avg, self.exp_avg_sq, self.step_count, self._hyper(),
                                   self._shapes())
         scheds = []
         if getattr(self, "scheduler", None) is not None:
@@ -147,7 +157,12 @@ class _TrainingState:
             opt = state
         else:
             raise ValueError("not a training state: neither 'optimizers' nor 'param_groups'")
-        self.step_count = optim_state_to_flat(opt, self.engine.keys, self.exp_avg, self.exp_avg_sq, self._shapes())
+        keys = self._state_keys()
+        if len(opt["param_groups"]) == 1 and len(opt["param_groups"][0]["params"]) != len(keys):
+            raise ValueError(f"optimizer state has {len(opt['param_groups'][0]['params'])} parameters, the trainer "
+                             f"has {len(keys)} trainable parameters (of {len(self.engine.keys)}): resume under the "
+                             "trainable mask the state was saved with")
+        self.step_count = optim_state_to_flat(opt, keys, self.exp_avg, self.exp_avg_sq, self._shapes())
         g = opt["param_groups"][0]
         self.lr, self.betas = float(g["lr"]), tuple(float(b) for b in g["betas"])
         self.eps, self.weight_decay = float(g["eps"]), float(g["weight_decay"])
@@ -264,12 +279,35 @@ class TrainEngine(_FlatEngine):
         # autograd leaves their .grad None and torch.optim skips them
         unused = ("output_param.", "refinement_out.") if not self.params_cat else ()
         self.used = [not k.startswith(unused) for k, _, _ in self.keys]
+        # kdlae_tt_set_trainable's mask, one bool per key (all True: no mask set on the handle)
+        self.trainable = [True] * len(self.keys)
+
+    def set_trainable(self, mask=None):
+        """Freeze parameters (``kdlae_tt_set_trainable``): ``mask`` holds one truth value per key in
+        ``named_parameters()`` order, True = trainable; ``None`` = all.  The backward then computes a layer's
+        weight gradient only for a trainable key and stops at the first layer that holds one; the forward keeps
+        no activations before it.  Frozen keys get exactly zero in ``grad``.  Not between a forward and its
+        backward; holds until changed."""
+        if mask is None:
+            rc = self._L.kdlae_tt_set_trainable(self.handle, None, 0)
+            new = [True] * len(self.keys)
+        else:
+            new = [bool(v) for v in mask]
+            buf = (ctypes.c_ubyte * len(new))(*[int(v) for v in new])
+            rc = self._L.kdlae_tt_set_trainable(self.handle, buf, len(new))
+        _lib.check(rc, "kdlae_tt_set_trainable")
+        self.trainable = new
+
+    def backward_launches(self) -> int:
+        """Launches the last backward issued (``kdlae_tt_debug_backward_launches``)."""
+        return int(self._L.kdlae_tt_debug_backward_launches(self.handle))
 
     def used_ranges(self):
-        """[begin, end) float ranges of the flat buffer that receive gradients (merged)."""
+        """[begin, end) float ranges of the flat buffer that receive gradients (merged): the keys the forward
+        uses that are trainable."""
         out = []
-        for (k, n, off), u in zip(self.keys, self.used):
-            if not u:
+        for (k, n, off), u, t in zip(self.keys, self.used, self.trainable):
+            if not (u and t):
                 continue
             end = off + ((n + 3) & ~3)  # keys are 16-byte aligned; the zero pad floats ride along
             if out and out[-1][1] == off:
@@ -318,6 +356,11 @@ class TeacherTrainFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, engine, img, rate, *params):
+        # frozen parameters (requires_grad False, e.g. after freeze_except_patch_embed_and_enhance): the
+        # engine skips their gradients and every layer before the first trainable one
+        mask = [bool(g) for g in ctx.needs_input_grad[3:]]
+        if mask != engine.trainable:
+            engine.set_trainable(None if all(mask) else mask)
         theta = engine.flatten(params)
         hq, sr = engine.forward(theta, img, rate)
         # an output the loss ignores arrives as None (not zeros), so the branch that produced only it
@@ -327,6 +370,7 @@ class TeacherTrainFn(torch.autograd.Function):
         ctx.generation = engine.generation
         ctx.theta = theta
         ctx.shapes = [p.shape for p in params]
+        ctx.mask = mask
         if sr is None:
             return hq
         return hq, sr
@@ -344,10 +388,27 @@ class TeacherTrainFn(torch.autograd.Function):
         # sr = enhance(cen(hq)) (KDLAE_model.py:324-329): with no sr gradient that branch is untouched
         skip = ("cen.", "upen.", "enhance.", "outputen.") if dsr is None else None
         grads = []
-        for (k, n, off), shape, used in zip(eng.keys, ctx.shapes, eng.used):
-            live = used and not (skip and k.startswith(skip))
+        for (k, n, off), shape, used, train in zip(eng.keys, ctx.shapes, eng.used, ctx.mask):
+            live = used and train and not (skip and k.startswith(skip))
             grads.append(grad[off:off + n].view(shape) if live else None)
         return (None, None, None, *grads)
+
+
+def freeze_except_patch_embed_and_enhance(model):
+    """The reference's fine-tuning freeze (Train/basicsr/train.py:24-55, used by 01_sures_param_fintune.yml,
+    03_param_fintue.yml, 05_sures_fintue.yml): every parameter's ``requires_grad`` becomes False except those of
+    ``patch_embed`` and, when ``model.static == "train"``, of the sr head ``cen``, ``upen``, ``enhance``,
+    ``outputen``.  Returns the model.  The training forward reads ``requires_grad``, so the drop-in and a
+    ``KDLAETrainer`` built afterwards get the cheaper backward."""
+    for p in model.parameters():
+        p.requires_grad = False
+    mods = [model.patch_embed]
+    if model.static == "train":
+        mods += [model.cen, model.upen, model.enhance, model.outputen]
+    for m in mods:
+        for p in m.parameters():
+            p.requires_grad = True
+    return model
 
 
 class _L1LossSrFn(torch.autograd.Function):
@@ -1135,9 +1196,11 @@ class KDLAETrainer(_TrainingState):
         self.step_count = 0
         self.output = None
         self.loss = None
-        ranges = eng.used_ranges()
-        self._ranges = (ctypes.c_int64 * (2 * len(ranges)))(*[v for r in ranges for v in r])
-        self._nranges = len(ranges) if len(ranges) != 1 or ranges[0] != [0, eng.numel] else 0
+        # frozen parameters (requires_grad False at construction, or set_trainable later)
+        mask = [bool(p.requires_grad) for p in params]
+        if not all(mask):
+            eng.set_trainable(mask)
+        self._set_ranges()
         L = _lib.lib()
         self._l1_scratch = torch.empty(int(L.kdlae_train_l1sr_scratch_floats()), dtype=torch.float32, device=dev)
         self._opt_scratch = torch.empty(int(L.kdlae_train_adamw_scratch_floats()), dtype=torch.float32, device=dev)
@@ -1149,6 +1212,34 @@ class KDLAETrainer(_TrainingState):
         # train.ema_decay (ImageCleanModel.__init__: net_g_ema starts as a copy of net_g, model_ema(0))
         self.ema_decay = float(ema_decay)
         self.theta_ema = self.theta.clone() if self.ema_decay > 0 else None
+
+    def _set_ranges(self):
+        """The [begin, end) ranges clip + AdamW updates: the used, trainable keys (frozen weights see neither
+        the update nor the weight decay, as torch.optim never holds them)."""
+        ranges = self.engine.used_ranges()
+        self._ranges = (ctypes.c_int64 * (2 * len(ranges)))(*[v for r in ranges for v in r])
+        self._nranges = len(ranges) if len(ranges) != 1 or ranges[0] != [0, self.engine.numel] else 0
+
+    def set_trainable(self, which=None):
+        """Choose the trainable parameters: ``which`` is an iterable of parameter names, a predicate
+        ``name -> bool``, or ``None`` for all.  Sets the parameters' ``requires_grad`` and the engine's mask;
+        frozen ``theta``, ``exp_avg`` and ``exp_avg_sq`` then keep their bits across ``step()``.  Call it between
+        iterations (not between ``forward_backward`` and ``step``)."""
+        names = [k for k, _, _ in self.engine.keys]
+        if which is None:
+            mask = [True] * len(names)
+        elif callable(which):
+            mask = [bool(which(k)) for k in names]
+        else:
+            want = set(which)
+            unknown = sorted(want - set(names))
+            if unknown:
+                raise ValueError(f"set_trainable: unknown parameter names {unknown[:4]}")
+            mask = [k in want for k in names]
+        self.engine.set_trainable(None if all(mask) else mask)
+        for p, t in zip(self.model.parameters(), mask):
+            p.requires_grad = t
+        self._set_ranges()
 
     def update_learning_rate(self, current_iter: int, warmup_iter: int = -1) -> float:
         """BaseModel.update_learning_rate (Train/basicsr/models/base_model.py:183-205): the scheduler
