@@ -98,6 +98,17 @@ typedef struct kdlae_t_handle kdlae_t_handle;
 
 /* replaces KDLAE_teacher.__init__ (KDLAE_model.py:205-268): validates the config, binds `device`. */
 int kdlae_t_create(const kdlae_t_config* cfg, int device, kdlae_t_handle** out);
+/* replaces Restormer.__init__ (Train/basicsr/models/archs/restormer_arch.py:471-546): a kdlae_t_handle whose
+ * parameter list is Restormer's own state_dict, in its order: patch_embed ... refinement, then output; none of
+ * output_param.*, refinement_out.*, output2.* or the sr head.  static_train and params_cat of `cfg` are ignored
+ * (Restormer has neither kwarg).  inp_channels != out_channels is KDLAE_EINVAL_CONFIG (the residual
+ * output(...) + inp_img, :559, is undefined), dual_pixel_task is KDLAE_ENOTIMPL (its 6-channel patch embed is
+ * wider than the narrow-input conv takes).  Every kdlae_t_* entry works on the handle: kdlae_t_forward computes
+ * hq = output(refinement(...)) + img with the launches of a KDLAE_teacher handle with params != 'cat' and
+ * static != 'train', bit for bit; `rate` and `sr` must be NULL (KDLAE_ESTATE otherwise, nothing launched);
+ * the rate sweep and the sr head are refused as on that teacher handle; the workspace holds no tail or sr-head
+ * buffer. */
+int kdlae_t_create_restormer(const kdlae_t_config* cfg, int device, kdlae_t_handle** out);
 int kdlae_t_destroy(kdlae_t_handle* h);
 
 /* state_dict surface (KDLAE_model.py:220-268 key layout; load_state_dict at KDLAE_T.ipynb:1074-1075).
@@ -122,7 +133,7 @@ int kdlae_t_set_param(kdlae_t_handle* h, const char* name, const float* host_dat
 int kdlae_t_commit_params(kdlae_t_handle* h, void* stream);
 
 /* Workspace contract, for every *_workspace_bytes query and every entry point that takes a `workspace` in this
- * header (kdlae_t_forward / _forward_rates / _forward_sr, kdlae_s_forward, asdqe_forward, kdlae_tt_*, kdlae_st_*,
+ * header (kdlae_t_forward / _forward_rates / _forward_sr (Restormer handles included), kdlae_s_forward, asdqe_forward, kdlae_tt_*, kdlae_st_*,
  * asdqe_train_*):
  *   - the query's answer is positive (-1 with kdlae_last_error for arguments the entry point would refuse) and a
  *     multiple of 256; `workspace` must be 256-byte aligned (every buffer the plan carves out of it then is);
@@ -360,6 +371,9 @@ typedef struct kdlae_tt_handle kdlae_tt_handle;
 
 /* replaces KDLAE_teacher.__init__ for training (same config struct; dual_pixel_task -> ENOTIMPL). */
 int kdlae_tt_create(const kdlae_t_config* cfg, int device, kdlae_tt_handle** out);
+/* replaces Restormer.__init__ for training: as kdlae_t_create_restormer, for a kdlae_tt_handle.  rate, sr and
+ * dsr must be NULL in kdlae_tt_forward / _backward / _backward_marked (KDLAE_ESTATE otherwise, nothing launched). */
+int kdlae_tt_create_restormer(const kdlae_t_config* cfg, int device, kdlae_tt_handle** out);
 int kdlae_tt_destroy(kdlae_tt_handle* h);
 /* net_g.state_dict() layout: key, element count and offset (floats) in the flat buffers. */
 int kdlae_tt_num_params(const kdlae_tt_handle* h);
@@ -424,6 +438,20 @@ int64_t kdlae_train_l1sr_scratch_floats(void);
 int kdlae_train_l1sr(const float* pred_hq, const float* gt_hq, int64_t n_hq, const float* pred_sr,
                      const float* gt_sr, int64_t n_sr, float* dhq, float* dsr, float* loss, float* scratch,
                      void* stream);
+/* replaces self.cri_pix(pred, self.gt) with L1LossSonar(loss_weight, reduction, binary)
+ * (Train/basicsr/models/losses/losses.py:25-65, Restomer.yml) over n floats:
+ *   reduction 0 = 'mean': loss[0] = loss_weight (mean|p - t| + mean|[p > binary] - [t > binary]|)
+ *   reduction 1 = 'sum':  both terms are sums
+ * The binarised term carries no gradient: dpred = sign(p - t) float32(loss_weight / n) ('mean') or
+ * sign(p - t) float32(loss_weight) ('sum'), exactly 0.0 on a tie; the comparison with `binary` is strictly >.
+ * dpred NULL = loss only.  `weight` is the loss's element-weight argument and must be NULL (ImageCleanModel
+ * never passes one, image_restoration_model.py:212).  reduction outside {0, 1} ('none'), a non-null weight, a null
+ * pred / target / loss / scratch or n <= 0: KDLAE_EINVAL_CONFIG; nothing is launched.  Two stages in a fixed order
+ * (per-block partials of at most 1024 blocks, one double sum over them in block order), no atomics: equal
+ * inputs give equal bits.  scratch: device buffer of kdlae_train_l1sonar_scratch_floats() floats. */
+int64_t kdlae_train_l1sonar_scratch_floats(void);
+int kdlae_train_l1sonar(const float* pred, const float* target, int64_t n, float loss_weight, float binary,
+                        int reduction, const float* weight, float* dpred, float* loss, float* scratch, void* stream);
 /* replaces torch.nn.utils.clip_grad_norm_(params, max_norm) + torch.optim.AdamW.step (:215-218) over
  * flat buffers: g = gscale * grad (gscale = 1/world_size after a summing all-reduce), clipped to
  * max_norm (<= 0: no clip); `step` counts from 1.  The norm covers all n gradients; the update

@@ -120,12 +120,13 @@ class _Engine:
     writes that bypass autograd's version counter (``p.data.mul_()``, BasicSR's ``model_ema``,
     base_model.py:54-62), optimizer steps and ``load_state_dict`` are always seen."""
 
-    def __init__(self, cfg, device_index: int, prefix: str = "kdlae_t"):
+    def __init__(self, cfg, device_index: int, prefix: str = "kdlae_t", create: str = "_create"):
+        """``create``: the suffix of the create entry (``_create_restormer``: a plain-Restormer ``kdlae_t`` handle)."""
         L = _lib.lib()
         h = ctypes.c_void_p()
         self.prefix = prefix
-        _lib.check(getattr(L, prefix + "_create")(ctypes.byref(cfg), device_index, ctypes.byref(h)),
-                   prefix + "_create")
+        _lib.check(getattr(L, prefix + create)(ctypes.byref(cfg), device_index, ctypes.byref(h)),
+                   prefix + create)
         self.handle = h
         self.device_index = device_index
         self.ws = None
@@ -558,6 +559,112 @@ class KDLAE_teacher(nn.Module):
 
 # BasicSR registers the same network under this name (Train/basicsr/models/archs/restormer_arch.py:566)
 RestormerSuperResolutionParam2 = KDLAE_teacher
+
+
+class Restormer(KDLAE_teacher):
+    """Plain Restormer (Train/basicsr/models/archs/restormer_arch.py:471-562), the paper's baseline
+    (paper202508/Restomer.yml), with the forward on the MI355X HIP path.
+
+    The reference's constructor kwargs and submodule tree: ``state_dict()`` holds Restormer's own keys
+    (``patch_embed`` ... ``refinement``, ``output``), so upstream Restormer checkpoints load and none of the
+    teacher's ``output_param.*`` / ``refinement_out.*`` / ``output2.*`` is read or written.
+    ``forward(x [B,C,H,W]) -> [B,C,H,W]`` = ``output(refinement(...)) + x``, H and W divisible by 8.
+
+    The network is ``KDLAE_teacher(params != 'cat', static != 'train')``'s and runs the same kernels in the same
+    order (``kdlae_t_create_restormer`` / ``kdlae_tt_create_restormer``); this class inherits the teacher's
+    plumbing (HIP-graph replay with an eager fallback in eval mode, ``forward_tiled``, the training engine behind
+    an autograd node in train mode, ``requires_grad`` read as the trainable mask) with tensors in place of dicts.
+    ``dual_pixel_task=True`` raises NotImplementedError."""
+
+    def __init__(self, inp_channels=3, out_channels=3, dim=48, num_blocks=[4, 6, 6, 8], num_refinement_blocks=4,
+                 heads=[1, 2, 4, 8], ffn_expansion_factor=2.66, bias=False, LayerNorm_type='WithBias',
+                 dual_pixel_task=False):
+        nn.Module.__init__(self)
+        if dual_pixel_task:
+            raise NotImplementedError("Restormer dual_pixel_task=True needs a 6-channel patch embed; the MI355X "
+                                      "build's narrow-input conv takes at most 4 channels")
+        if inp_channels != out_channels:
+            raise RuntimeError(f"Restormer: inp_channels ({inp_channels}) must equal out_channels ({out_channels}): "
+                               "the residual output(...) + inp_img is undefined otherwise")
+        self.params, self.static, self.dual_pixel_task = "none", "none", False
+        self._cfg = dict(inp_channels=inp_channels, out_channels=out_channels, dim=dim,
+                         num_blocks=list(num_blocks), num_refinement_blocks=num_refinement_blocks,
+                         heads=list(heads), ffn_expansion_factor=ffn_expansion_factor, bias=bias,
+                         LayerNorm_type=LayerNorm_type, dual_pixel_task=False, static="none", params="none")
+        d, nb, hd, f, ln = dim, num_blocks, heads, ffn_expansion_factor, LayerNorm_type
+        self.patch_embed = OverlapPatchEmbed(inp_channels, d)
+        self.encoder_level1 = _stage(nb[0], d, hd[0], f, bias, ln)
+        self.down1_2 = Downsample(d)
+        self.encoder_level2 = _stage(nb[1], 2 * d, hd[1], f, bias, ln)
+        self.down2_3 = Downsample(2 * d)
+        self.encoder_level3 = _stage(nb[2], 4 * d, hd[2], f, bias, ln)
+        self.down3_4 = Downsample(4 * d)
+        self.latent = _stage(nb[3], 8 * d, hd[3], f, bias, ln)
+        self.up4_3 = Upsample(8 * d)
+        self.reduce_chan_level3 = nn.Conv2d(8 * d, 4 * d, kernel_size=1, bias=bias)
+        self.decoder_level3 = _stage(nb[2], 4 * d, hd[2], f, bias, ln)
+        self.up3_2 = Upsample(4 * d)
+        self.reduce_chan_level2 = nn.Conv2d(4 * d, 2 * d, kernel_size=1, bias=bias)
+        self.decoder_level2 = _stage(nb[1], 2 * d, hd[1], f, bias, ln)
+        self.up2_1 = Upsample(2 * d)
+        self.decoder_level1 = _stage(nb[0], 2 * d, hd[0], f, bias, ln)
+        self.refinement = _stage(num_refinement_blocks, 2 * d, hd[0], f, bias, ln)
+        self.output = nn.Conv2d(2 * d, out_channels, kernel_size=3, padding=1, bias=bias)
+        self._engines = {}
+        self._train_engines = {}
+        self._warned_grad = False
+
+    def engine(self, device: torch.device) -> _Engine:
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        eng = self._engines.get(idx)
+        if eng is None:
+            eng = _Engine(self._c_config(), idx, create="_create_restormer")
+            self._engines[idx] = eng
+        return eng
+
+    def forward(self, inp_img):
+        x = inp_img
+        if not torch.is_tensor(x):
+            raise RuntimeError("Restormer.forward takes a tensor [B,C,H,W] (KDLAE_teacher takes the dict)")
+        if x.device.type != "cuda":
+            raise RuntimeError("Restormer (MI355X build) runs on ROCm devices only; move the model inputs to "
+                               "'cuda' — there is no CPU fallback")
+        if x.dim() != 4 or x.shape[1] != self._cfg["inp_channels"]:
+            raise RuntimeError(f"expected x [B,{self._cfg['inp_channels']},H,W], got {tuple(x.shape)}")
+        H, W = x.shape[-2:]
+        if H % 8 or W % 8:
+            raise RuntimeError(f"Restormer needs H and W divisible by 8, got {H}x{W}")
+        wants_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if wants_grad and not self.training and not self._warned_grad:
+            warnings.warn("Restormer in eval mode with grad enabled: the HIP inference path returns outputs "
+                          "without an autograd graph; call .train() to differentiate through the model")
+            self._warned_grad = True
+        if wants_grad and self.training:
+            if x.requires_grad and not self._warned_grad:
+                warnings.warn("Restormer HIP training path: the input image receives no gradient")
+                self._warned_grad = True
+            from .train import RestormerTrainEngine, TeacherTrainFn
+            eng = self._train_engines.get(x.device.index)
+            if eng is None:
+                eng = RestormerTrainEngine(self, x.device)
+                self._train_engines[x.device.index] = eng
+            return TeacherTrainFn.apply(eng, x, None, *self.parameters())
+        if self.hip_graphs and not torch.cuda.is_current_stream_capturing():
+            return self._forward_graphed(x, None)["hq"]
+        return self._forward_eager(x, None)["hq"]
+
+    def forward_tiled(self, inp_img, tile=512, tile_overlap=32, tile_batch=16):
+        """``forward`` over overlapping tiles blended on the device (upstream Restormer's ``--tile`` /
+        ``--tile_overlap``; ``KDLAE_teacher.forward_tiled`` states the plan): ``[B,C,H,W] -> [B,C,H,W]``."""
+        self._check_inference_input(inp_img, "forward_tiled")
+        with torch.no_grad():
+            return self._forward_tiled(inp_img, None, tile, tile_overlap, tile_batch)["hq"]
+
+    def forward_rates(self, *args, **kwargs):
+        raise RuntimeError("Restormer has no denoise_rate input: forward_rates is KDLAE_teacher's")
+
+    def forward_sr(self, *args, **kwargs):
+        raise RuntimeError("Restormer has no sr head: forward_sr is KDLAE_teacher's")
 
 
 def _conv_block3d(cin, cout, k, pad):

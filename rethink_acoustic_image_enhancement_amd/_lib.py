@@ -22,7 +22,7 @@ ERRORS = {0: "OK", 1: "EINVAL_SHAPE", 2: "EINVAL_CONFIG", 3: "EHIP", 4: "EPARAM"
 # Every entry point include/kdlae.h declares (checked by tests/test_abi.py).
 EXPORTS = (
     "kdlae_last_error", "kdlae_abi_version",
-    "kdlae_t_create", "kdlae_t_destroy", "kdlae_t_num_params", "kdlae_t_param_info",
+    "kdlae_t_create", "kdlae_t_create_restormer", "kdlae_t_destroy", "kdlae_t_num_params", "kdlae_t_param_info",
     "kdlae_t_set_param", "kdlae_t_commit_params", "kdlae_t_params_numel", "kdlae_t_prepare", "kdlae_t_pack_device",
     "kdlae_t_workspace_bytes", "kdlae_t_forward",
     "kdlae_t_rates_workspace_bytes", "kdlae_t_forward_rates", "kdlae_t_sr_workspace_bytes", "kdlae_t_forward_sr",
@@ -36,7 +36,7 @@ EXPORTS = (
     "asdqe_create", "asdqe_destroy", "asdqe_num_params", "asdqe_param_info", "asdqe_set_param",
     "asdqe_commit_params", "asdqe_params_numel", "asdqe_prepare", "asdqe_pack_device", "asdqe_workspace_bytes", "asdqe_forward",
     "kdlae_padded_size", "kdlae_preprocess_u8", "kdlae_frames_preprocess_u8", "kdlae_postprocess_u8",
-    "kdlae_tt_create", "kdlae_tt_destroy", "kdlae_tt_num_params", "kdlae_tt_param_info", "kdlae_tt_num_floats",
+    "kdlae_tt_create", "kdlae_tt_create_restormer", "kdlae_tt_destroy", "kdlae_tt_num_params", "kdlae_tt_param_info", "kdlae_tt_num_floats",
     "kdlae_tt_workspace_bytes", "kdlae_tt_forward", "kdlae_tt_backward", "kdlae_tt_backward_marked",
     "kdlae_tt_mark_count", "kdlae_tt_mark_lo", "kdlae_tt_mark_wait", "kdlae_tt_mark_sync",
     "kdlae_tt_set_trainable", "kdlae_tt_is_trainable", "kdlae_tt_debug_backward_launches",
@@ -45,6 +45,7 @@ EXPORTS = (
     "kdlae_st_create", "kdlae_st_destroy", "kdlae_st_num_params", "kdlae_st_param_info", "kdlae_st_num_floats",
     "kdlae_st_workspace_bytes", "kdlae_st_forward", "kdlae_st_backward",
     "kdlae_train_l1frames_scratch_floats", "kdlae_train_l1frames",
+    "kdlae_train_l1sonar_scratch_floats", "kdlae_train_l1sonar",
     "kdlae_debug_tgemm",
     "kdlae_debug_gemm",
     "kdlae_debug_gemm_variant",
@@ -207,6 +208,7 @@ def lib() -> ctypes.CDLL:
     L.kdlae_last_error.restype = c_char_p
     L.kdlae_abi_version.restype = c_int
     L.kdlae_t_create.argtypes = [ctypes.POINTER(TConfig), c_int, ctypes.POINTER(c_void_p)]
+    L.kdlae_t_create_restormer.argtypes = L.kdlae_t_create.argtypes
     L.kdlae_t_destroy.argtypes = [c_void_p]
     L.kdlae_t_num_params.argtypes = [c_void_p]
     L.kdlae_t_param_info.argtypes = [c_void_p, c_int, ctypes.POINTER(c_char_p), ctypes.POINTER(c_int64)]
@@ -272,6 +274,7 @@ def lib() -> ctypes.CDLL:
     L.kdlae_postprocess_u8.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
                                        c_void_p, c_void_p]
     L.kdlae_tt_create.argtypes = [ctypes.POINTER(TConfig), c_int, ctypes.POINTER(c_void_p)]
+    L.kdlae_tt_create_restormer.argtypes = L.kdlae_tt_create.argtypes
     L.kdlae_tt_destroy.argtypes = [c_void_p]
     L.kdlae_tt_num_params.argtypes = [c_void_p]
     L.kdlae_tt_param_info.argtypes = [c_void_p, c_int, ctypes.POINTER(c_char_p), ctypes.POINTER(c_int64),
@@ -322,6 +325,10 @@ def lib() -> ctypes.CDLL:
     L.kdlae_train_l1frames_scratch_floats.restype = c_int64
     L.kdlae_train_l1frames.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int64, ctypes.c_float, ctypes.c_float,
                                        ctypes.c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.kdlae_train_l1sonar_scratch_floats.argtypes = []
+    L.kdlae_train_l1sonar_scratch_floats.restype = c_int64
+    L.kdlae_train_l1sonar.argtypes = [c_void_p, c_void_p, c_int64, ctypes.c_float, ctypes.c_float, c_int, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p]
     L.asdqe_train_create.argtypes = [ctypes.POINTER(AConfig), c_int, ctypes.POINTER(c_void_p)]
     L.asdqe_train_destroy.argtypes = [c_void_p]
     L.asdqe_train_num_params.argtypes = [c_void_p]

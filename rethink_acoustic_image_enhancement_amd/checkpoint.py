@@ -64,3 +64,48 @@ def load_network(net: torch.nn.Module, load_path: str, strict: bool = True, para
                 load_net[k + ".ignore"] = load_net.pop(k)
     res = net.load_state_dict(load_net, strict=strict)
     return list(res.missing_keys), list(res.unexpected_keys)
+
+
+def _as_state_dict(path_or_sd, param_key="params") -> dict:
+    if isinstance(path_or_sd, dict):
+        sd = path_or_sd
+        for k in (param_key, "params", "params_ema"):
+            if k and k in sd and isinstance(sd[k], dict):
+                sd = sd[k]
+                break
+        return _strip_module(dict(sd))
+    return read_state_dict(path_or_sd, param_key)
+
+
+def load_restormer(model: torch.nn.Module, path_or_sd, strict: bool = False, param_key: str | None = "params"):
+    """``pretrain_network_g`` + ``strict_load_g: false`` of paper202508/Restomer.yml for a ``KDLAE_model.Restormer``:
+    an upstream Restormer checkpoint (a path, a ``{'params': sd}`` dict or a bare state_dict) loaded the way
+    ``load_network`` does it; with ``strict=False`` a key whose shape differs from the module's is left out and
+    reported as missing.  Returns (missing, unexpected) keys."""
+    sd = _as_state_dict(path_or_sd, param_key)
+    if not strict:
+        crt = model.state_dict()
+        for k in list(sd):
+            if k in crt and crt[k].size() != sd[k].size():
+                sd[k + ".ignore"] = sd.pop(k)
+    res = model.load_state_dict(sd, strict=strict)
+    return list(res.missing_keys), list(res.unexpected_keys)
+
+
+def restormer_trunk_into_teacher(teacher: torch.nn.Module, sd, param_key: str | None = "params"):
+    """Warm-start a ``KDLAE_teacher`` from a Restormer checkpoint (KDLAET.yml ``strict_load_g: false``): every key
+    of ``sd`` (a path, a ``{'params': sd}`` dict or a state_dict) that the teacher has with the same shape is
+    copied; the teacher's own keys (``output_param.*``, ``refinement_out.*``, ``output2.*``, the sr head) keep
+    their values.  Returns (copied, skipped): the keys taken, and the checkpoint keys the teacher lacks or holds
+    with another shape."""
+    src = _as_state_dict(sd, param_key)
+    dst = teacher.state_dict()
+    copied, skipped = [], []
+    with torch.no_grad():
+        for k, v in src.items():
+            if k in dst and dst[k].size() == v.size():
+                dst[k].copy_(v)
+                copied.append(k)
+            else:
+                skipped.append(k)
+    return copied, skipped

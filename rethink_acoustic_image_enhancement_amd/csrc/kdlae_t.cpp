@@ -59,6 +59,10 @@ using namespace kdlae;
 
 struct kdlae_t_handle : HandleBase {
   kdlae_t_config cfg{};
+  // plain Restormer (kdlae_t_create_restormer): the keys end at `output`, nothing of the rate tail or the
+  // sr head is packed or planned; cfg.params_cat == cfg.static_train == 0, so the forward takes the
+  // teacher's no-cat / no-sr route launch for launch
+  bool restormer = false;
   // model (the TransformerBlock stages are listed by stages() below)
   std::vector<BlockW> enc1, enc2, enc3, latent, dec3, dec2, dec1, refinement, refinement_out, enhance;
   SmallW patch_embed, output, output_param, output2, cen, outputen;
@@ -85,9 +89,13 @@ struct kdlae_t_handle : HandleBase {
 
 namespace kdlae {
 
-static int validate(const kdlae_t_config& c) {
+static int validate(const kdlae_t_config& c, bool restormer = false) {
   if (c.dual_pixel_task)
-    return fail(KDLAE_ENOTIMPL, "dual_pixel_task=True: the reference forward raises NameError (out_hq undefined, KDLAE_model.py:305-321)");
+    return fail(KDLAE_ENOTIMPL, restormer ? "Restormer dual_pixel_task=True needs a 6-channel patch embed; the narrow-input conv takes Cin <= 4"
+                                          : "dual_pixel_task=True: the reference forward raises NameError (out_hq undefined, KDLAE_model.py:305-321)");
+  if (restormer && c.inp_channels != c.out_channels)
+    return fail(KDLAE_EINVAL_CONFIG, "Restormer: inp_channels (" + std::to_string(c.inp_channels) + ") must equal out_channels (" +
+                                         std::to_string(c.out_channels) + "): the residual output(...) + inp_img is undefined otherwise (restormer_arch.py:559)");
   if (c.dim <= 0 || c.dim % 16)
     return fail(KDLAE_EINVAL_CONFIG, "dim must be a positive multiple of 16 on the HIP path");
   if (c.inp_channels < 1 || c.inp_channels > 4 || c.out_channels < 1 || c.out_channels > 3)
@@ -126,7 +134,7 @@ struct Stage {
   bool runs;    // the forward runs it: refinement_out only for params == "cat", enhance only for static == "train"
   int part;     // 0 trunk (sees only the image), 1 rate-dependent tail, 2 sr head: a rate sweep batches them apart
 };
-static std::vector<Stage> stages(const kdlae_t_config& c) {
+static std::vector<Stage> stages(const kdlae_t_config& c, bool restormer) {
   using H = kdlae_t_handle;
   const int d = c.dim, nr = c.num_refinement_blocks;
   const int *nb = c.num_blocks, *hd = c.heads;
@@ -140,7 +148,7 @@ static std::vector<Stage> stages(const kdlae_t_config& c) {
       {"decoder_level2", nb[1], 2 * d, hd[1], 1, 2, &H::dec2, true, true, 0},
       {"decoder_level1", nb[0], 2 * d, hd[0], 1, 1, &H::dec1, true, true, 0},
       {"refinement", nr, 2 * d, hd[0], 1, 1, &H::refinement, true, true, 0},
-      {"refinement_out", nr, 2 * d, hd[0], 1, 1, &H::refinement_out, true, cat, 1},
+      {"refinement_out", nr, 2 * d, hd[0], 1, 1, &H::refinement_out, !restormer, cat, 1},
       {"enhance", nr, d, hd[0], 2, 1, &H::enhance, sr, sr, 2},
   };
 }
@@ -415,13 +423,14 @@ static Plan make_plan(const kdlae_t_handle* h, const int (&Bn)[3], int H, int W,
   pl.lat = pl.take(P4 * 8 * d);
   pl.dec3 = pl.take(P3 * 4 * d);
   pl.dec2 = pl.take(P2 * 2 * d);
-  pl.out4 = pl.take(Pt * 4);
-  pl.refo = pl.take(Pt * 2 * d);
+  // the rate tail's buffers: only the params == 'cat' route (rate_tail, run_rates) touches them
+  pl.out4 = c.params_cat ? pl.take(Pt * 4) : 0;
+  pl.refo = c.params_cat ? pl.take(Pt * 2 * d) : 0;
   pl.cenb = c.static_train && h->sr_fold == kNone ? pl.take(Ps * 2 * d) : 0;  // cen's output: unfolded sr head only
   pl.srs = c.static_train ? pl.take(4 * Ps * d) : 0;
   // per-block scratch: max over every packed stage (refinement_out too when the forward skips it)
   long long mq = 0, mv = 0, mfp = 0, mfg = 0, mst = 0, mpart = 0, mred = 0, mM = 0;
-  for (const Stage& st : stages(c)) {
+  for (const Stage& st : stages(c, h->restormer)) {
     const int Hh = H * st.num / st.den, Ww = W * st.num / st.den;
     const long long Bs = Bn[st.part];
     const long long P = Bs * Hh * Ww;
@@ -989,6 +998,22 @@ int kdlae_t_create(const kdlae_t_config* cfg, int device, kdlae_t_handle** out) 
   return KDLAE_OK;
 }
 
+int kdlae_t_create_restormer(const kdlae_t_config* cfg, int device, kdlae_t_handle** out) {
+  if (!cfg || !out) return fail(KDLAE_ESTATE, "null argument");
+  *out = nullptr;
+  kdlae_t_config c = *cfg;
+  c.static_train = c.params_cat = 0;  // Restormer has neither kwarg
+  int rc = validate(c, true);
+  if (rc) return rc;
+  auto* h = new kdlae_t_handle();
+  h->cfg = c;
+  h->restormer = true;
+  h->device = device;
+  restormer_keys(h->cfg, h->ps.lay);
+  *out = h;
+  return KDLAE_OK;
+}
+
 int kdlae_t_destroy(kdlae_t_handle* h) {
   if (!h) return KDLAE_OK;
   handle_release(h);
@@ -1031,8 +1056,10 @@ static int record_program(HandleBase* base, PackProgram& prog) {
   h->reduce2 = pk.pointwise("reduce_chan_level2", 2 * d, 4 * d, 4 * d, 2 * d, [](int n) { return n; }, "", c.bias, false);
   h->up2_1 = pk.conv3("up2_1.body.0", 4 * d, 2 * d, 2);
   h->output = pk.small("output", c.out_channels, 2 * d, c.bias);
-  h->output_param = pk.small("output_param", 2 * d, c.out_channels + 1, c.bias);
-  h->output2 = pk.small("output2", c.out_channels, 2 * d, c.bias);
+  if (!h->restormer) {
+    h->output_param = pk.small("output_param", 2 * d, c.out_channels + 1, c.bias);
+    h->output2 = pk.small("output2", c.out_channels, 2 * d, c.bias);
+  }
   if (c.static_train) {
     const int hc = 2 * d;
     if (sr_fold_supported(c.out_channels, 2 * hc / 16) && !debug_flag("no_sr_fold")) {
@@ -1050,7 +1077,7 @@ static int record_program(HandleBase* base, PackProgram& prog) {
     }
     h->outputen = pk.small("outputen", c.out_channels, hc / 2, c.bias);
   }
-  for (const Stage& st : stages(c))
+  for (const Stage& st : stages(c, h->restormer))
     if (st.packed) h->*st.blocks = pk.stage(st);
   return pk.err;
 }
@@ -1085,6 +1112,7 @@ int kdlae_t_forward(kdlae_t_handle* h, const float* img, const float* rate, int 
     return fail(KDLAE_EINVAL_SHAPE, "KDLAE_teacher needs H % 8 == 0 and W % 8 == 0 (pixel_unshuffle x3, KDLAE_model.py:187)");
   if (!img || !hq) return fail(KDLAE_ESTATE, "img and hq are required");
   if (h->cfg.params_cat && !rate) return fail(KDLAE_ESTATE, "denoise_rate is required when params=='cat'");
+  if (h->restormer && rate) return fail(KDLAE_ESTATE, "a Restormer handle takes no denoise_rate: rate must be null");
   if ((sr != nullptr) != (h->cfg.static_train != 0))
     return fail(KDLAE_ESTATE, "sr must be non-null iff static=='train'");
   Fwd f{h, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<char*>(workspace), make_plan(h, B, H, W), B};
@@ -1199,7 +1227,7 @@ int64_t kdlae_t_debug_sr_fold(const kdlae_t_handle* h, float* dst, int64_t capac
 struct TapInfo { std::string name; int C, num, den; };
 static std::vector<TapInfo> tap_list(const kdlae_t_handle* h) {
   std::vector<TapInfo> v;
-  for (const Stage& st : stages(h->cfg)) {
+  for (const Stage& st : stages(h->cfg, h->restormer)) {
     if (!st.runs || st.count <= 0) continue;
     const std::string n = st.name;
     v.push_back({n + ".in", st.C, st.num, st.den});

@@ -62,6 +62,7 @@ using TouchMap = std::map<int64_t, std::pair<int, int>>;
 
 struct kdlae_tt_handle : kdlae::TrainHandleBase {
   kdlae_t_config cfg{};
+  bool restormer = false;  // kdlae_tt_create_restormer: Restormer's own key list, the no-cat / no-sr route
   Saved sv;
   int ws_B = -1, ws_H = -1, ws_W = -1;  // last kdlae_tt_workspace_bytes query (its dry run is cached)
   int64_t ws_bytes = -1;
@@ -122,9 +123,13 @@ struct kdlae_tt_handle : kdlae::TrainHandleBase {
 
 namespace {
 
-int validate(const kdlae_t_config& c) {
+int validate(const kdlae_t_config& c, bool restormer = false) {
   if (c.dual_pixel_task)
-    return fail(KDLAE_ENOTIMPL, "dual_pixel_task=True: the reference forward raises NameError (KDLAE_model.py:305-321)");
+    return fail(KDLAE_ENOTIMPL, restormer ? "Restormer dual_pixel_task=True needs a 6-channel patch embed; the narrow-input conv takes Cin <= 4"
+                                          : "dual_pixel_task=True: the reference forward raises NameError (KDLAE_model.py:305-321)");
+  if (restormer && c.inp_channels != c.out_channels)
+    return fail(KDLAE_EINVAL_CONFIG, "Restormer: inp_channels (" + std::to_string(c.inp_channels) + ") must equal out_channels (" +
+                                         std::to_string(c.out_channels) + "): the residual output(...) + inp_img is undefined otherwise (restormer_arch.py:559)");
   if (c.dim <= 0 || c.dim % 2 || 8 * c.dim > 512)
     return fail(KDLAE_EINVAL_CONFIG, "training path: dim must be even and 8*dim <= 512 (LayerNorm wave kernel)");
   if (c.inp_channels < 1 || c.inp_channels != c.out_channels)
@@ -1348,6 +1353,22 @@ int kdlae_tt_create(const kdlae_t_config* cfg, int device, kdlae_tt_handle** out
   return KDLAE_OK;
 }
 
+int kdlae_tt_create_restormer(const kdlae_t_config* cfg, int device, kdlae_tt_handle** out) {
+  if (!cfg || !out) return fail(KDLAE_EINVAL_CONFIG, "null argument");
+  kdlae_t_config c = *cfg;
+  c.static_train = c.params_cat = 0;  // Restormer has neither kwarg
+  int rc = validate(c, true);
+  if (rc) return rc;
+  auto* h = new kdlae_tt_handle();
+  h->cfg = c;
+  h->restormer = true;
+  h->device = device;
+  kdlae::restormer_keys(h->cfg, h->lay);
+  build_order(h);
+  *out = h;
+  return KDLAE_OK;
+}
+
 int kdlae_tt_destroy(kdlae_tt_handle* h) { return kdlae::train_destroy(h); }
 
 // a null handle has 0 parameters here (-1 in kdlae_st_* and asdqe_train_*)
@@ -1433,6 +1454,8 @@ int kdlae_tt_forward(kdlae_tt_handle* h, const float* theta, const float* img, c
   int rc = check_shape(B, H, W);
   if (rc) return rc;
   if (h->cfg.params_cat && !rate) return fail(KDLAE_EINVAL_CONFIG, "params='cat' needs denoise_rate");
+  if (h->restormer && (rate || sr))
+    return fail(KDLAE_ESTATE, "a Restormer handle takes no denoise_rate and gives no sr: both must be null");
   if (h->cfg.static_train && !sr) return fail(KDLAE_EINVAL_CONFIG, "static='train' needs the sr output");
   const int64_t need = kdlae_tt_workspace_bytes(h, B, H, W);
   if (need < 0 || (size_t)need > ws_bytes) return fail(KDLAE_ESTATE, "training workspace too small");
@@ -1463,6 +1486,7 @@ static int bwd_fits(kdlae_tt_handle* h, size_t ws_bytes) {
 int kdlae_tt_backward(kdlae_tt_handle* h, const float* theta, const float* dhq, const float* dsr, float* grad, void* ws,
                       size_t ws_bytes, void* stream) {
   if (!h || !theta || !grad || !ws) return fail(KDLAE_EINVAL_CONFIG, "null argument");
+  if (h->restormer && dsr) return fail(KDLAE_ESTATE, "a Restormer handle has no sr output: dsr must be null");
   TRY(h->sv.check(ws, "kdlae_tt_backward", "kdlae_tt_forward"));
   TRY(bwd_fits(h, ws_bytes));
   const bool has_dsr = h->cfg.static_train && dsr;
@@ -1477,6 +1501,7 @@ int kdlae_tt_backward(kdlae_tt_handle* h, const float* theta, const float* dhq, 
 int kdlae_tt_backward_marked(kdlae_tt_handle* h, const float* theta, const float* dhq, const float* dsr, float* grad,
                              void* ws, size_t ws_bytes, void* stream) {
   if (!h || !theta || !grad || !ws) return fail(KDLAE_EINVAL_CONFIG, "null argument");
+  if (h->restormer && dsr) return fail(KDLAE_ESTATE, "a Restormer handle has no sr output: dsr must be null");
   TRY(h->sv.check(ws, "kdlae_tt_backward_marked", "kdlae_tt_forward"));
   TRY(bwd_fits(h, ws_bytes));
   const bool has_dsr = h->cfg.static_train && dsr;

@@ -48,7 +48,7 @@ std::vector<float> ParamStore::flat() const {
 
 // KDLAE_teacher (KDLAE_model.py:220-268, TransformerBlock :150-157, Attention :113-120,
 // FeedForward :90-99, LayerNorm :73-79)
-void teacher_keys(const kdlae_t_config& c, ParamLayout& out) {
+static void trunk_and_tail(const kdlae_t_config& c, bool tail, ParamLayout& out) {
   auto conv = [&](const std::string& n, int co, int ci, int k, bool b) {
     out.add(n + ".weight", (int64_t)co * ci * k * k);
     if (b) out.add(n + ".bias", co);
@@ -89,6 +89,7 @@ void teacher_keys(const kdlae_t_config& c, ParamLayout& out) {
   stage("decoder_level1", nb[0], 2 * d, hd[0]);
   stage("refinement", nr, 2 * d, hd[0]);
   conv("output", c.out_channels, 2 * d, 3, c.bias);
+  if (!tail) return;
   conv("output_param", 2 * d, c.out_channels + 1, 3, c.bias);
   stage("refinement_out", nr, 2 * d, hd[0]);
   conv("output2", c.out_channels, 2 * d, 3, c.bias);
@@ -100,6 +101,12 @@ void teacher_keys(const kdlae_t_config& c, ParamLayout& out) {
     conv("outputen", c.out_channels, hc / 2, 3, c.bias);
   }
 }
+
+void teacher_keys(const kdlae_t_config& c, ParamLayout& out) { trunk_and_tail(c, true, out); }
+
+// Restormer (Train/basicsr/models/archs/restormer_arch.py:471-546): the teacher's keys up to and including
+// `output`; no output_param / refinement_out / output2 and no sr head (dual_pixel_task's skip_conv is refused)
+void restormer_keys(const kdlae_t_config& c, ParamLayout& out) { trunk_and_tail(c, false, out); }
 
 // KDLAE_student (KDLAE_model.py:359-384).  The reference registers encoders, pooling, st_fusion,
 // upconv_layers, decoders, out_conv in that attribute order; state_dict() lists encoders.*, st_fusion.*,

@@ -53,6 +53,8 @@ inline int hid_of(const kdlae_t_config& c, int dim) { return (int)((double)dim *
 // The key enumerators: state_dict order of the reference modules.  KDLAE_teacher and KDLAE_student have
 // no buffers, so state_dict() and named_parameters() list the same keys.
 void teacher_keys(const kdlae_t_config& c, ParamLayout& out);
+// plain Restormer: patch_embed ... refinement, output (the teacher's list without the rate tail and the sr head)
+void restormer_keys(const kdlae_t_config& c, ParamLayout& out);
 void student_keys(const kdlae_s_config& c, ParamLayout& out);
 // DenoiseRatePredictor: with `buffers` the BatchNorm running_mean / running_var / num_batches_tracked
 // entries are included (state_dict order, the inference handle); without, the parameters alone

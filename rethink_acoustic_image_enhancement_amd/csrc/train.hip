@@ -1599,6 +1599,55 @@ hipError_t launch_l1sr_final(const float* part0, int nblk0, long long n0, float 
   return hipGetLastError();
 }
 
+// L1LossSonar (Train/basicsr/models/losses/losses.py:25-65): part[blk] = (sum |p - t|, sum |[p > binary] - [t > binary]|)
+// and the gradient gscale sign(p - t) (torch.where's binarisation carries none; sign(0) = 0).  As l1sr_kernel, with
+// the threshold an argument and only the blocks that see data launched (kSonarBlocks at most).
+constexpr int kSonarBlocks = 1024;
+__global__ __launch_bounds__(256) void l1sonar_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
+                                                      long long n, float binary, float gscale,
+                                                      float* __restrict__ grad, float* __restrict__ part) {
+  __shared__ float sh[4];
+  float a = 0.f, sb = 0.f;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const float p = pred[i], t = tgt[i];
+    const float d = p - t;
+    a += fabsf(d);
+    sb += fabsf((p > binary ? 1.f : 0.f) - (t > binary ? 1.f : 0.f));
+    if (grad) grad[i] = d > 0.f ? gscale : (d < 0.f ? -gscale : 0.f);
+  }
+  a = block_sum_256(a, sh);
+  sb = block_sum_256(sb, sh);
+  if (threadIdx.x == 0) {
+    part[2 * blockIdx.x] = a;
+    part[2 * blockIdx.x + 1] = sb;
+  }
+}
+
+// loss = w (S_l1 + S_bin) inv: the block partials summed in double in block order, one rounding to fp32
+__global__ void l1sonar_final_kernel(const float* __restrict__ part, int nblk, float w, double inv,
+                                     float* __restrict__ loss) {
+  if (threadIdx.x != 0) return;
+  double a = 0.0, b = 0.0;
+  for (int i = 0; i < nblk; ++i) {
+    a += part[2 * i];
+    b += part[2 * i + 1];
+  }
+  loss[0] = (float)(w * ((a + b) * inv));
+}
+
+int l1sonar_scratch_floats() { return 2 * kSonarBlocks; }
+
+hipError_t launch_l1sonar(const float* pred, const float* target, long long n, float loss_weight, float binary,
+                          int sum_reduction, float* dpred, float* loss, float* scratch, hipStream_t s) {
+  const double inv = sum_reduction ? 1.0 : 1.0 / (double)n;
+  const long long want = (n + 255) / 256;
+  const int nblk = want < kSonarBlocks ? (int)want : kSonarBlocks;
+  const float gscale = sum_reduction ? loss_weight : (float)(loss_weight / (double)n);
+  hipLaunchKernelGGL(l1sonar_kernel, dim3(nblk), dim3(256), 0, s, pred, target, n, binary, gscale, dpred, scratch);
+  hipLaunchKernelGGL(l1sonar_final_kernel, dim3(1), dim3(64), 0, s, scratch, nblk, loss_weight, inv, loss);
+  return hipGetLastError();
+}
+
 __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, long long n, float* __restrict__ part) {
   __shared__ float sh[4];
   float a = 0.f;

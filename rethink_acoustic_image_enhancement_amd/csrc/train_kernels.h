@@ -220,6 +220,12 @@ hipError_t launch_l1sr(const float* pred, const float* target, long long n, floa
 hipError_t launch_l1sr_final(const float* part0, int nblk0, long long n0, float wl0, float ws0, const float* part1,
                              int nblk1, long long n1, float wl1, float ws1, float* out, hipStream_t s);
 
+// L1LossSonar (losses.py:25-65): loss[0] = w red(|p - t| + |[p > binary] - [t > binary]|), red = mean (0) / sum (1);
+// dpred (nullable) = sign(p - t) float32(w / n) or float32(w).  scratch: l1sonar_scratch_floats() floats.
+int l1sonar_scratch_floats();
+hipError_t launch_l1sonar(const float* pred, const float* target, long long n, float loss_weight, float binary,
+                          int sum_reduction, float* dpred, float* loss, float* scratch, hipStream_t s);
+
 // grad-norm clip + AdamW (torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW, base_model.py / image_restoration_model.py:216-218)
 hipError_t launch_sumsq(const float* g, long long n, float* part, int nblk, hipStream_t s);
 // state[0] = total norm of (gscale * g), state[1] = gscale * min(1, max_norm / (norm + 1e-6)) (or gscale if max_norm <= 0)

@@ -48,6 +48,20 @@ int kdlae_train_l1frames(const float* pred, const float* target, int N, int fram
   return KDLAE_OK;
 }
 
+int64_t kdlae_train_l1sonar_scratch_floats(void) { return tr::l1sonar_scratch_floats(); }
+
+int kdlae_train_l1sonar(const float* pred, const float* target, int64_t n, float loss_weight, float binary,
+                        int reduction, const float* weight, float* dpred, float* loss, float* scratch, void* stream) {
+  if (!pred || !target || !loss || !scratch) return fail(KDLAE_EINVAL_CONFIG, "null argument");
+  if (n <= 0) return fail(KDLAE_EINVAL_CONFIG, "empty loss input");
+  if (reduction != 0 && reduction != 1)
+    return fail(KDLAE_EINVAL_CONFIG, "reduction: 0 = 'mean', 1 = 'sum' ('none' is not implemented)");
+  if (weight)
+    return fail(KDLAE_EINVAL_CONFIG, "L1LossSonar element weights are not implemented (ImageCleanModel passes none)");
+  HIPCHK(tr::launch_l1sonar(pred, target, n, loss_weight, binary, reduction, dpred, loss, scratch, (hipStream_t)stream));
+  return KDLAE_OK;
+}
+
 int kdlae_train_mse(const float* score, const float* target, int n, float scale, float* dscore, float* loss,
                     void* stream) {
   if (!score || !target || !dscore || !loss) return fail(KDLAE_ESTATE, "null argument");

@@ -73,9 +73,20 @@ def postprocess_u8(out: torch.Tensor, h: int, w: int, scale: int = 1, lq_u8: tor
     return dst
 
 
+def _is_restormer(model) -> bool:
+    from .KDLAE_model import Restormer
+    return isinstance(model, Restormer)
+
+
 def enhance_u8(model, images: torch.Tensor, denoise_rate, bgr: bool = False, multiple: int = 8):
-    """KDLAE_T.ipynb inference for u8 images [B,h,w,C] on the model's device -> (hq u8, sr u8 or None)."""
+    """KDLAE_T.ipynb inference for u8 images [B,h,w,C] on the model's device -> (hq u8, sr u8 or None).
+    A ``KDLAE_model.Restormer`` takes the image alone: ``denoise_rate`` is ignored (pass None), no rate map is
+    made and ``sr`` is None."""
     B, h, w, C = images.shape
+    if _is_restormer(model):
+        img, _ = preprocess_u8(images, None, multiple, bgr)
+        with torch.no_grad():
+            return postprocess_u8(model(img), h, w, 1, images), None
     img, rmap = preprocess_u8(images, denoise_rate, multiple, bgr)
     with torch.no_grad():
         pred = model({"img": img, "denoise_rate": rmap})
@@ -92,6 +103,9 @@ def enhance_tiled_u8(model, images: torch.Tensor, denoise_rate, tile: int = 512,
     the pixels of each tile), as it is in upstream Restormer's tiled demo; it equals it when one tile covers
     the padded image."""
     B, h, w, C = images.shape
+    if _is_restormer(model):
+        img, _ = preprocess_u8(images, None, multiple, bgr)
+        return postprocess_u8(model.forward_tiled(img, tile, tile_overlap, tile_batch), h, w, 1, images), None
     img, rmap = preprocess_u8(images, denoise_rate, multiple, bgr)
     pred = model.forward_tiled({"img": img, "denoise_rate": rmap}, tile, tile_overlap, tile_batch)
     hq = postprocess_u8(pred["hq"], h, w, 1, images)

@@ -30,7 +30,8 @@ __all__ = ["TrainEngine", "TeacherTrainFn", "L1LossSr", "KDLAETrainer", "MixingA
            "grad_buckets", "sync_gradients_bucketed", "StudentTrainEngine", "StudentTrainFn",
            "L1LossForVideoFrames", "KDLAESTrainer", "AsdqeTrainEngine", "AsdqeTrainFn", "asdqe_train_forward",
            "asdqe_dropout_masks", "ASDQETrainer", "flat_to_optim_state", "optim_state_to_flat",
-           "freeze_except_patch_embed_and_enhance"]
+           "freeze_except_patch_embed_and_enhance", "RestormerTrainEngine", "L1LossSonar", "RestormerTrainer",
+           "CosineAnnealingRestartCyclicLR"]
 
 
 def _vp(t):
@@ -210,12 +211,12 @@ class _FlatEngine:
     (``keys``: ``(name, numel, offset)`` in ``named_parameters()`` order, every key 16-byte aligned; ``numel``:
     floats of the flat buffer) and the workspace ``ws``, grown on demand."""
 
-    def __init__(self, prefix, model, device: torch.device, what):
+    def __init__(self, prefix, model, device: torch.device, what, create="create"):
         L = _lib.lib()
         self._L, self._prefix, self.device = L, prefix, device
         h = ctypes.c_void_p()
         idx = device.index if device.index is not None else torch.cuda.current_device()
-        _lib.check(self._fn("create")(ctypes.byref(model._c_config()), idx, ctypes.byref(h)), prefix + "_create")
+        _lib.check(self._fn(create)(ctypes.byref(model._c_config()), idx, ctypes.byref(h)), f"{prefix}_{create}")
         self.handle = h
         self._dtor = self._fn("destroy")
         self.keys = []
@@ -269,8 +270,8 @@ class _FlatEngine:
 class TrainEngine(_FlatEngine):
     """``kdlae_tt_*`` handle for one KDLAE_teacher config on one device."""
 
-    def __init__(self, model, device: torch.device):
-        super().__init__("kdlae_tt", model, device, "KDLAE_teacher")
+    def __init__(self, model, device: torch.device, what="KDLAE_teacher", create="create"):
+        super().__init__("kdlae_tt", model, device, what, create)
         cfg = model._cfg
         self.static_train = cfg["static"] == "train"
         self.params_cat = cfg["params"] == "cat"
@@ -351,8 +352,17 @@ class TrainEngine(_FlatEngine):
         return [int(self._L.kdlae_tt_mark_lo(self.handle, j)) for j in range(self._L.kdlae_tt_mark_count(self.handle))]
 
 
+class RestormerTrainEngine(TrainEngine):
+    """``kdlae_tt_*`` handle made by ``kdlae_tt_create_restormer`` for one ``KDLAE_model.Restormer`` on one device:
+    Restormer's own key list, the teacher's no-cat / no-sr launches; ``forward(theta, x, None) -> (out, None)``."""
+
+    def __init__(self, model, device: torch.device):
+        super().__init__(model, device, "Restormer", "create_restormer")
+
+
 class TeacherTrainFn(torch.autograd.Function):
-    """Autograd node for one KDLAE_teacher forward on the training engine."""
+    """Autograd node for one KDLAE_teacher (or Restormer: ``rate`` None, one output) forward on the training
+    engine."""
 
     @staticmethod
     def forward(ctx, engine, img, rate, *params):
@@ -464,6 +474,61 @@ class L1LossSr(torch.nn.Module):
             raise RuntimeError("L1LossSr (MI355X build) runs on ROCm devices only")
         return _L1LossSrFn.apply(pred["hq"], target["hq"], pred.get("sr"), target.get("sr") if pred.get("sr")
                                  is not None else None, float(self.loss_weight))
+
+
+_REDUCTIONS = {"mean": 0, "sum": 1}
+
+
+def _l1sonar(pred, target, loss_weight, binary, reduction, dpred, loss, scratch):
+    """``kdlae_train_l1sonar`` over contiguous fp32 tensors; ``dpred`` None = loss only."""
+    rc = _lib.lib().kdlae_train_l1sonar(_vp(pred), _vp(target), pred.numel(), float(loss_weight), float(binary),
+                                        _REDUCTIONS[reduction], None, _vp(dpred), _vp(loss), _vp(scratch),
+                                        _stream(pred.device))
+    _lib.check(rc, "kdlae_train_l1sonar")
+
+
+class _L1LossSonarFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, loss_weight, binary, reduction):
+        dev = pred.device
+        p = pred.detach().to(torch.float32).contiguous()
+        t = target.detach().to(device=dev, dtype=torch.float32).contiguous()
+        dp = torch.empty_like(p) if ctx.needs_input_grad[0] else None
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        scratch = torch.empty(int(_lib.lib().kdlae_train_l1sonar_scratch_floats()), dtype=torch.float32, device=dev)
+        _l1sonar(p, t, loss_weight, binary, reduction, dp, loss, scratch)
+        ctx.dp = dp
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        # g == 1 (l_pix.backward()) leaves the kernel's bits: x * 1.0f is exact
+        return (ctx.dp * g if ctx.dp is not None else None), None, None, None, None
+
+
+class L1LossSonar(torch.nn.Module):
+    """L1LossSonar (Train/basicsr/models/losses/losses.py:25-65, Restomer.yml's pixel_opt) on the HIP path,
+    autograd-aware: loss_weight * (red|p - t| + red|[p > binary] - [t > binary]|), red = 'mean' or 'sum'; the
+    binarised term carries no gradient (``kdlae_train_l1sonar``)."""
+
+    def __init__(self, loss_weight=1.0, reduction='mean', binary=0.1):
+        super().__init__()
+        if reduction not in ("none", "mean", "sum"):
+            raise ValueError(f"Unsupported reduction mode: {reduction}. Supported ones are: ['none', 'mean', 'sum']")
+        if reduction == "none":
+            raise NotImplementedError("the HIP L1LossSonar implements reduction='mean' and 'sum'")
+        self.loss_weight = loss_weight
+        self.reduction = reduction
+        self.binary = binary
+
+    def forward(self, pred, target, weight=None, **kwargs):
+        if weight is not None:
+            raise NotImplementedError("element-wise loss weights are not used by the reference configs")
+        if pred.device.type != "cuda":
+            raise RuntimeError("L1LossSonar (MI355X build) runs on ROCm devices only")
+        if pred.shape != target.shape:
+            raise RuntimeError(f"L1LossSonar: pred {tuple(pred.shape)} and target {tuple(target.shape)} differ")
+        return _L1LossSonarFn.apply(pred, target, float(self.loss_weight), float(self.binary), self.reduction)
 
 
 # ------------------------------------------------------------------ KDLAE-S (KDLAES.yml)
@@ -1156,21 +1221,23 @@ class CosineAnnealingRestartCyclicLR:
             1 + math.cos(math.pi * ((last_epoch - nearest_restart) / self.periods[idx])))
 
 
-class KDLAETrainer(_TrainingState):
-    """ImageCleanModel.optimize_parameters for KDLAE_teacher (image_restoration_model.py:198-218).
+class _ImageCleanTrainer(_TrainingState):
+    """ImageCleanModel.optimize_parameters (image_restoration_model.py:198-218) over a ``kdlae_tt_*`` handle's
+    flat buffers: everything the KDLAE-T and the Restormer trainer share.  A subclass names its engine
+    (``_engine_cls``), its loss scratch (``_loss_scratch_floats``), how a batch reaches the network and the loss
+    (``_forward_loss``) and how a validation pair is read (``_val_pair``)."""
 
-    Defaults follow Train/Denoising/Options/paper202508/KDLAET.yml: AdamW lr 1e-5,
-    weight_decay 5e-5, betas (0.2, 0.999); use_grad_clip -> clip_grad_norm_(0.01); L1LossSr."""
+    _engine_cls = None
 
     def __init__(self, model, lr=1e-5, weight_decay=0.5e-4, betas=(0.2, 0.999), eps=1e-8, use_grad_clip=True,
                  max_norm=0.01, loss_weight=1.0, group=None, mixing_augs=None, ema_decay=0.0, scheduler=None,
                  bucket_cap_mb=25.0, overlap_grad_reduce=True):
         params = list(model.parameters())
         if not params or params[0].device.type != "cuda":
-            raise RuntimeError("KDLAETrainer: move the model to a ROCm device first (no CPU fallback)")
+            raise RuntimeError(f"{type(self).__name__}: move the model to a ROCm device first (no CPU fallback)")
         dev = params[0].device
         self.model = model
-        self.engine = TrainEngine(model, dev)
+        self.engine = self._engine_cls(model, dev)
         eng = self.engine
         # flat parameter buffer; the module's parameters become views of it
         self.theta = eng.flatten(params).contiguous()
@@ -1202,7 +1269,7 @@ class KDLAETrainer(_TrainingState):
             eng.set_trainable(mask)
         self._set_ranges()
         L = _lib.lib()
-        self._l1_scratch = torch.empty(int(L.kdlae_train_l1sr_scratch_floats()), dtype=torch.float32, device=dev)
+        self._l1_scratch = torch.empty(self._loss_scratch_floats(), dtype=torch.float32, device=dev)
         self._opt_scratch = torch.empty(int(L.kdlae_train_adamw_scratch_floats()), dtype=torch.float32, device=dev)
         self._loss = torch.zeros((), dtype=torch.float32, device=dev)
         # KDLAET.yml train.mixing_augs ({mixup, mixup_beta, use_identity}); ImageCleanModel.__init__ :83-87
@@ -1251,8 +1318,9 @@ class KDLAETrainer(_TrainingState):
             self.lr = self.init_lr / warmup_iter * current_iter
         return self.lr
 
-    def feed_train_data(self, lq: dict, gt: dict):
-        """ImageCleanModel.feed_train_data (:161-186): the optional mixup of (gt, lq)."""
+    def feed_train_data(self, lq, gt):
+        """ImageCleanModel.feed_train_data (:161-186): the optional mixup of (gt, lq); dicts of tensors
+        (KDLAE-T) or bare tensors (Restormer)."""
         if self.mixing is not None:
             gt, lq = self.mixing(gt, lq)
         return lq, gt
@@ -1286,7 +1354,8 @@ class KDLAETrainer(_TrainingState):
     def validate(self, batches, window_size=8, crop_border=0, use_image=False, use_ema=None, metrics=("psnr",),
                  niqe=False, niqe_params=None, tile=None, tile_overlap=32, tile_batch=16):
         """ImageCleanModel.nondist_validation with pad_test (image_restoration_model.py:226-348) over
-        ``(lq, gt)`` pairs, ``lq = {'img', 'denoise_rate'}``, ``gt = {'hq', 'sr'}``: reflect-pad ``img`` and the
+        ``(lq, gt)`` pairs, ``lq = {'img', 'denoise_rate'}``, ``gt = {'hq', 'sr'}`` (RestormerTrainer: two
+        tensors, and only the ``*_hq`` results): reflect-pad ``img`` and the
         rate map right and bottom to a multiple of ``window_size``, run the inference engine
         (``kdlae_t_forward``), and take the PSNR of the top-left h x w window of ``hq`` (2h x 2w of ``sr``)
         against its target.  Returns ``{'psnr_hq': mean, 'psnr_sr': mean}`` over all images (``psnr_sr`` only
@@ -1316,11 +1385,10 @@ class KDLAETrainer(_TrainingState):
         flat = _inference_flat(self, self.theta_ema if use_ema else self.theta)
         hqs, srs, s_hqs, s_srs, seen = [], [], [], [], False
         for lq, gt in batches:
-            img = lq["img"]
+            img, rate, gt = self._val_pair(lq, gt)
             if img.device.type != "cuda":
                 raise RuntimeError("KDLAE validation runs on ROCm devices only; there is no CPU fallback")
             h, w = img.shape[-2:]
-            rate = lq.get("denoise_rate") if self.engine.params_cat else None
             img_p = _reflect_pad(img.to(torch.float32), window_size)
             rate_p = _reflect_pad(rate.to(device=img.device, dtype=torch.float32), window_size) if rate is not None \
                 else None
@@ -1354,31 +1422,18 @@ class KDLAETrainer(_TrainingState):
     def _distributed(self) -> bool:
         return dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1
 
-    def forward_backward(self, lq: dict, gt: dict, marked: bool = False):
+    def forward_backward(self, lq, gt, marked: bool = False):
         """preds = net_g(lq); l_pix = cri_pix(preds, gt); l_pix.backward()  (:198-213).
 
         ``marked``: record gradient-ready marks and build ``self.buckets`` for the overlapped all-reduce."""
-        eng, L = self.engine, _lib.lib()
-        hq, sr = eng.forward(self.theta, lq["img"], lq.get("denoise_rate"))
-        self.output = {"hq": hq, "sr": sr}
-        dhq = torch.empty_like(hq)
-        dsr = torch.empty_like(sr) if sr is not None else None
-        gt_hq = gt["hq"].to(torch.float32).contiguous()
-        gt_sr = gt["sr"].to(torch.float32).contiguous() if sr is not None else None
-        rc = L.kdlae_train_l1sr(_vp(hq), _vp(gt_hq), hq.numel(), _vp(sr), _vp(gt_sr), sr.numel() if sr is not None
-                                else 0, _vp(dhq), _vp(dsr), _vp(self._loss), _vp(self._l1_scratch),
-                                _stream(hq.device))
-        _lib.check(rc, "kdlae_train_l1sr")
-        if self.loss_weight != 1.0:
-            dhq.mul_(self.loss_weight)
-            if dsr is not None:
-                dsr.mul_(self.loss_weight)
+        eng = self.engine
+        dhq, dsr, loss = self._forward_loss(lq, gt)
         if marked:
             self.buckets = grad_buckets(eng.backward(self.theta, dhq, dsr, self.grad, marked=True), eng.numel,
                                         self.bucket_cap_floats)
         else:
             eng.backward(self.theta, dhq, dsr, self.grad)
-        self.loss = self._loss * self.loss_weight
+        self.loss = loss
         return self.loss
 
     def step(self, gscale: float = 1.0):
@@ -1396,8 +1451,8 @@ class KDLAETrainer(_TrainingState):
                                             self.ema_decay, _stream(self.theta.device))
             _lib.check(rc, "kdlae_train_ema")
 
-    def optimize_parameters(self, lq: dict, gt: dict):
-        """One full iteration: forward, L1LossSr, backward, DDP all-reduce, clip, AdamW.  With several
+    def optimize_parameters(self, lq, gt):
+        """One full iteration: forward, the loss, backward, DDP all-reduce, clip, AdamW.  With several
         ranks the all-reduce runs in gradient buckets overlapped with the backward (overlap_grad_reduce)."""
         if self._distributed() and self.overlap_grad_reduce:
             loss = self.forward_backward(lq, gt, marked=True)
@@ -1414,3 +1469,68 @@ class KDLAETrainer(_TrainingState):
 
     def get_current_log(self):
         return {"l_pix": float(self.loss)} if self.loss is not None else {}
+
+
+class KDLAETrainer(_ImageCleanTrainer):
+    """ImageCleanModel.optimize_parameters for KDLAE_teacher (image_restoration_model.py:198-218).
+
+    Defaults follow Train/Denoising/Options/paper202508/KDLAET.yml: AdamW lr 1e-5,
+    weight_decay 5e-5, betas (0.2, 0.999); use_grad_clip -> clip_grad_norm_(0.01); L1LossSr.
+    ``lq = {'img', 'denoise_rate'}``, ``gt = {'hq', 'sr'}``."""
+
+    _engine_cls = TrainEngine
+
+    def _loss_scratch_floats(self):
+        return int(_lib.lib().kdlae_train_l1sr_scratch_floats())
+
+    def _val_pair(self, lq, gt):
+        return lq["img"], (lq.get("denoise_rate") if self.engine.params_cat else None), gt
+
+    def _forward_loss(self, lq, gt):
+        hq, sr = self.engine.forward(self.theta, lq["img"], lq.get("denoise_rate"))
+        self.output = {"hq": hq, "sr": sr}
+        dhq = torch.empty_like(hq)
+        dsr = torch.empty_like(sr) if sr is not None else None
+        gt_hq = gt["hq"].to(torch.float32).contiguous()
+        gt_sr = gt["sr"].to(torch.float32).contiguous() if sr is not None else None
+        rc = _lib.lib().kdlae_train_l1sr(_vp(hq), _vp(gt_hq), hq.numel(), _vp(sr), _vp(gt_sr),
+                                         sr.numel() if sr is not None else 0, _vp(dhq), _vp(dsr), _vp(self._loss),
+                                         _vp(self._l1_scratch), _stream(hq.device))
+        _lib.check(rc, "kdlae_train_l1sr")
+        if self.loss_weight != 1.0:
+            dhq.mul_(self.loss_weight)
+            if dsr is not None:
+                dsr.mul_(self.loss_weight)
+        return dhq, dsr, self._loss * self.loss_weight
+
+
+class RestormerTrainer(_ImageCleanTrainer):
+    """ImageCleanModel.optimize_parameters for ``KDLAE_model.Restormer`` with paper202508/Restomer.yml: tensor
+    ``lq`` / ``gt`` [B,C,H,W], the optional mixup, forward, ``L1LossSonar(loss_weight, reduction, binary)``
+    (``kdlae_train_l1sonar``), backward, clip_grad_norm_(0.01) + AdamW (lr 1e-5, weight_decay 5e-5, betas
+    (0.2, 0.999)), EMA, CosineAnnealingRestartCyclicLR.  ``validate`` returns the ``*_hq`` metrics of the
+    output; ``training_state`` / ``resume_training`` / ``set_trainable`` / ``group=`` as ``KDLAETrainer``."""
+
+    _engine_cls = RestormerTrainEngine
+
+    def __init__(self, model, *args, reduction="mean", binary=0.1, **kwargs):
+        if reduction not in _REDUCTIONS:
+            raise NotImplementedError("the HIP L1LossSonar implements reduction='mean' and 'sum'")
+        self.reduction, self.binary = reduction, binary
+        super().__init__(model, *args, **kwargs)
+
+    def _loss_scratch_floats(self):
+        return int(_lib.lib().kdlae_train_l1sonar_scratch_floats())
+
+    def _val_pair(self, lq, gt):
+        return lq, None, {"hq": gt}
+
+    def _forward_loss(self, lq, gt):
+        out, _ = self.engine.forward(self.theta, lq, None)
+        self.output = out
+        dout = torch.empty_like(out)
+        gt_c = gt.to(device=out.device, dtype=torch.float32).contiguous()
+        if gt_c.shape != out.shape:
+            raise RuntimeError(f"RestormerTrainer: gt {tuple(gt_c.shape)} does not match the output {tuple(out.shape)}")
+        _l1sonar(out, gt_c, self.loss_weight, self.binary, self.reduction, dout, self._loss, self._l1_scratch)
+        return dout, None, self._loss.clone()
