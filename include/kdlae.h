@@ -222,6 +222,23 @@ int kdlae_tile_gather(const float* src, int B, int C, int H, int W, int tile, in
 int kdlae_tile_blend(const float* tiles, int B, int C, int H, int W, int tile, int overlap, int scale, float* dst,
                      void* stream);
 
+/* The blend of a tiled rate sweep: all R outputs in one launch, read from the staging layout the sweep leaves.
+ * kdlae_t_forward_rates at batch `count` writes [R][count][C][th][tw]; run over the n = B ni nj tiles of the plan
+ * tile_batch at a time, each chunk into its own block, it leaves the chunk-major buffer `staged`
+ * (T = C scale^2 th tw floats per tile; scale 1: hq, scale 2: sr):
+ *   chunk k holds tiles k tile_batch .. k tile_batch + count_k - 1, count_k = min(tile_batch, n - k tile_batch),
+ *   and starts at float k tile_batch R T;
+ *   inside chunk k, rate r and tile q (flat index k tile_batch + q) sit at (r count_k + q) T;
+ *   n R T floats in all, no padding (tile_batch >= n is the one chunk [R][n][C][scale th][scale tw]).
+ * Writes dst [R][B][C][scale H][scale W]: per output pixel 0 + o1 + o2 + ... over the covering tiles in ascending
+ * flat tile index, in fp32, divided by the fp32 count, so dst[r] has exactly the bits kdlae_tile_blend gives for
+ * the r-th slice re-laid out as [n][C][scale th][scale tw], for every tile_batch.  One thread per output pixel
+ * group, no atomics; 16-byte accesses where both pointers and the x stride allow, 4-byte otherwise.
+ * Null pointers, R outside 1..64, B, C or tile_batch < 1, scale outside {1, 2}: KDLAE_EINVAL_CONFIG; the plan's
+ * refusals as above.  Every check comes before the launch. */
+int kdlae_tile_blend_rates(const float* staged, int R, int B, int C, int H, int W, int tile, int overlap,
+                           int tile_batch, int scale, float* dst, void* stream);
+
 /* Measurement hook for bench.py (no effect on results).  When a probe class is armed, every
  * launch of that kernel class inside kdlae_t_forward is bracketed by a pair of HIP events on
  * `stream`; kdlae_t_probe_read synchronises those events and returns the summed device time (ms),

@@ -528,6 +528,94 @@ class KDLAE_teacher(nn.Module):
         _lib.check(rc, "kdlae_t_forward_rates")
         return {"hq": hq, "sr": srt}
 
+    # ------------------------------------------------------------------ tiled rate sweep
+    def forward_rates_tiled(self, img, rates, sr=False, tile=512, tile_overlap=32, tile_batch=16):
+        """``forward_rates`` for images larger than one forward can hold: the tiles of ``forward_tiled``'s plan go
+        through ``kdlae_t_forward_rates`` ``tile_batch`` at a time (the trunk runs once per tile, the rate tail at
+        batch R * count), every chunk writes its block of a chunk-major staging buffer, and one
+        ``kdlae_tile_blend_rates`` launch per output blends all R results (tiling.py, include/kdlae.h).
+
+        ``rates``: R scalars, ``[R, B]`` or ``[R, B, 1, H, W]`` maps, as ``forward_rates`` takes them.  Returns
+        ``{"hq": [R,B,C,H,W], "sr": [R,B,C,2H,2W] or None}``; ``hq[r]`` / ``sr[r]`` are bit for bit what
+        ``forward_tiled`` gives with ``denoise_rate = rates[r]`` as a map, for every ``tile_batch``.  The staging
+        holds R outputs of every tile (R * B * ni * nj tiles of C * th * tw floats, five times that with ``sr``).
+        Eval mode, eager (no HIP-graph replay), no autograd graph."""
+        with torch.no_grad():
+            plan, rt, st_hq, st_sr = self._sweep_tiles(img, rates, sr, tile, tile_overlap, tile_batch)
+            from . import tiling
+            B, _, H, W = img.shape
+            R = rt.shape[0]
+            hq = tiling.tile_blend_rates(st_hq, R, B, H, W, tile, tile_overlap, tile_batch, 1)
+            srt = tiling.tile_blend_rates(st_sr, R, B, H, W, tile, tile_overlap, tile_batch, 2) if sr else None
+        return {"hq": hq, "sr": srt}
+
+    def _sweep_tiles(self, img, rates, sr, tile, tile_overlap, tile_batch):
+        """The sweep on gathered tiles -> (plan, rates as given ([R,B] or maps), hq staging, sr staging or None):
+        flat fp32 buffers in ``kdlae_tile_blend_rates``' chunk-major layout.  Every refusal comes before the first
+        launch and before the staging is allocated."""
+        from . import tiling
+        self._check_inference_input(img, "forward_rates_tiled")
+        ci, oc = self._cfg["inp_channels"], self._cfg["out_channels"]
+        if img.dim() != 4 or img.shape[1] != ci:
+            raise RuntimeError(f"expected img [B,{ci},H,W], got {tuple(img.shape)}")
+        B, _, H, W = img.shape
+        if int(tile_batch) < 1:
+            raise RuntimeError(f"tile_batch must be at least 1, got {tile_batch}")
+        plan = tiling.tile_plan(H, W, tile, tile_overlap)   # refuses a bad shape / tile / overlap
+        if self._cfg["params"] != "cat":
+            raise RuntimeError("forward_rates_tiled needs params='cat': with params='plus' the forward never reads "
+                               "denoise_rate")
+        if sr and self.static != "train":
+            raise RuntimeError("forward_rates_tiled(sr=True) needs static='train': the model has no sr head")
+        dev = img.device
+        rt = torch.as_tensor(rates, dtype=torch.float32).detach().to(dev)
+        if rt.dim() == 1:
+            rt = rt[:, None].expand(-1, B)
+        is_map = rt.dim() == 5
+        R = rt.shape[0] if rt.dim() else 0
+        if not (tuple(rt.shape) == (R, B) or tuple(rt.shape) == (R, B, 1, H, W)):
+            raise RuntimeError(f"rates must be R scalars, [R,B] or [R,B,1,H,W] with B,H,W = {B, H, W}, got "
+                               f"{tuple(rt.shape)}")
+        if not 1 <= R <= 64:
+            raise RuntimeError(f"forward_rates_tiled takes 1..64 rates, got {R}")
+        rt = rt.contiguous()
+        th, tw, per = plan.th, plan.tw, plan.ni * plan.nj
+        n = B * per
+        tb = min(int(tile_batch), n)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        eng = self.engine(dev)
+        L = _lib.lib()
+        eng.sync_params(self, stream)
+        # sized for the largest chunk and for the tail chunk, whichever needs more
+        sizes = [L.kdlae_t_rates_workspace_bytes(eng.handle, c, R, th, tw, int(bool(sr))) for c in {tb, n % tb or tb}]
+        if min(sizes) < 0:
+            _lib.check(1, "kdlae_t_rates_workspace_bytes")
+        ws = eng.workspace(max(sizes), dev)
+        img_c = img.detach().to(torch.float32).contiguous()
+        T = oc * th * tw
+        st_hq = torch.empty((n * R * T,), device=dev, dtype=torch.float32)
+        st_sr = torch.empty((n * R * 4 * T,), device=dev, dtype=torch.float32) if sr else None
+        # tile -> image, on the device: a chunk's [R, count] scalars are one index_select, no host round trip
+        image_of = None if is_map else torch.arange(n, device=dev) // per
+        for first in range(0, n, tb):
+            count = min(tb, n - first)
+            t_img = tiling.tile_gather(img_c, tile, tile_overlap, first, count)
+            if is_map:
+                t_rate = torch.empty((R, count, 1, th, tw), device=dev, dtype=torch.float32)
+                for r in range(R):
+                    tiling.tile_gather(rt[r], tile, tile_overlap, first, count, out=t_rate[r])
+            else:
+                t_rate = rt.index_select(1, image_of[first:first + count]).contiguous()
+            hq_k = st_hq[first * R * T:]
+            sr_k = st_sr[first * R * 4 * T:] if sr else None
+            rc = L.kdlae_t_forward_rates(eng.handle, ctypes.c_void_p(t_img.data_ptr()),
+                                         ctypes.c_void_p(t_rate.data_ptr()), int(is_map), count, R, th, tw,
+                                         ctypes.c_void_p(hq_k.data_ptr()),
+                                         ctypes.c_void_p(sr_k.data_ptr() if sr else 0),
+                                         ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.c_void_p(stream))
+            _lib.check(rc, "kdlae_t_forward_rates")
+        return plan, rt, st_hq, st_sr
+
     def forward_sr(self, hq):
         """The sr head alone on an (unclamped) ``hq`` [B,C,H,W] -> ``sr`` [B,C,2H,2W]: the bits ``forward``
         gives for the same ``hq``.  Needs static='train'.  Eval mode, eager."""
@@ -662,6 +750,9 @@ class Restormer(KDLAE_teacher):
 
     def forward_rates(self, *args, **kwargs):
         raise RuntimeError("Restormer has no denoise_rate input: forward_rates is KDLAE_teacher's")
+
+    def forward_rates_tiled(self, *args, **kwargs):
+        raise RuntimeError("Restormer has no denoise_rate input: forward_rates_tiled is KDLAE_teacher's")
 
     def forward_sr(self, *args, **kwargs):
         raise RuntimeError("Restormer has no sr head: forward_sr is KDLAE_teacher's")

@@ -1,5 +1,5 @@
-// Tiled inference (kdlae_tile_plan, kdlae_tile_gather, kdlae_tile_blend): both kernels move bytes, the blend
-// also adds and divides.
+// Tiled inference (kdlae_tile_plan, kdlae_tile_gather, kdlae_tile_blend, kdlae_tile_blend_rates): the kernels move
+// bytes, the blends also add and divide.
 //
 //   plan                per axis of length L: t = min(tile, L), stride = t - overlap, starts
 //                       range(0, L - t, stride) + [L - t], so n = ceil((L - t) / stride) + 1 (1 when L == t) and
@@ -10,6 +10,12 @@
 //                       ascending flat index (i outer, j inner), acc = 0 + o1 + o2 + ... in fp32, then divides by
 //                       the fp32 count: E.add_(patch); W.add_(1); E.div_(W) of the host loop, bit for bit.
 //                       No atomics.  scale 2 (the sr output) is the same plan with every coordinate doubled.
+//   tile_blend_rates_kernel  the same blend for the R outputs of a tiled rate sweep in one launch: dst
+//                       [R][B][C][sH][sW] from the chunk-major staging kdlae_t_forward_rates leaves when it runs
+//                       on the n = B ni nj tiles tile_batch at a time: chunk k (count_k = min(tile_batch,
+//                       n - k tile_batch) tiles) at float k tile_batch R T, rate r / tile q inside it at
+//                       (r count_k + q) T, T = C s^2 th tw.  Same cover loop, same sum order, same division, so
+//                       dst[r] has the bits tile_blend_kernel gives for the r-th slice laid out [n][C][sth][stw].
 //
 // V = 4 (float4 loads and stores) when both base pointers sit on 16 bytes and every tile start along x is a
 // multiple of 4 floats (H, W and tile are multiples of 8, so that is a condition on the stride alone); V = 1
@@ -116,6 +122,56 @@ __global__ __launch_bounds__(256) void tile_blend_kernel(const float* __restrict
   }
 }
 
+template <int V>
+__global__ __launch_bounds__(256) void tile_blend_rates_kernel(const float* __restrict__ staged,
+                                                               float* __restrict__ dst, TileGeo g, int C, int R, int B,
+                                                               int tile_batch, int ntiles, long long total) {
+  const int wq = g.Lx / V;
+  const long long T = (long long)C * g.ty * g.tx;  // floats of one staged tile
+  for (long long idx = blockIdx.x * 256LL + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
+    const long long row = idx / wq;  // over R B C Ly
+    const int X = (int)(idx - row * wq) * V;
+    const int Y = (int)(row % g.Ly);
+    const long long rbc = row / g.Ly;
+    const int c = (int)(rbc % C);
+    const int rb = (int)(rbc / C);
+    const int b = rb % B, r = rb / B;
+    const Cover cy = tile_cover(Y, g.Ly, g.ty, g.sy, g.ni), cx = tile_cover(X, g.Lx, g.tx, g.sx, g.nj);
+    float acc[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) acc[e] = 0.f;
+    int cnt = 0;
+    for (int ii = cy.lo; ii <= cy.hi + cy.last; ++ii) {
+      const int i = ii <= cy.hi ? ii : g.ni - 1;
+      const int yt = Y - (ii <= cy.hi ? i * g.sy : g.Ly - g.ty);
+      for (int jj = cx.lo; jj <= cx.hi + cx.last; ++jj) {
+        const int j = jj <= cx.hi ? jj : g.nj - 1;
+        const int xt = X - (jj <= cx.hi ? j * g.sx : g.Lx - g.tx);
+        const int flat = (b * g.ni + i) * g.nj + j;
+        const int k = flat / tile_batch, q = flat - k * tile_batch;
+        const int cnt_k = min(tile_batch, ntiles - k * tile_batch);
+        const long long slot = (long long)k * tile_batch * R + (long long)r * cnt_k + q;
+        const float* __restrict__ t = staged + slot * T + ((long long)c * g.ty + yt) * g.tx + xt;
+        if constexpr (V == 4) {
+          const float4 v = *reinterpret_cast<const float4*>(t);
+          acc[0] += v.x;
+          acc[1] += v.y;
+          acc[2] += v.z;
+          acc[3] += v.w;
+        } else {
+          acc[0] += *t;
+        }
+        ++cnt;
+      }
+    }
+    const float w = (float)cnt;
+    if constexpr (V == 4)
+      reinterpret_cast<float4*>(dst)[idx] = make_float4(acc[0] / w, acc[1] / w, acc[2] / w, acc[3] / w);
+    else
+      dst[idx] = acc[0] / w;
+  }
+}
+
 static int axis_tiles(int L, int t, int stride) { return L == t ? 1 : (int)ceil_div(L - t, stride) + 1; }
 
 // the argument checks every entry shares; `who` names the entry in the message
@@ -196,6 +252,36 @@ extern "C" int kdlae_tile_blend(const float* tiles, int B, int C, int H, int W, 
   else
     hipLaunchKernelGGL(tile_blend_kernel<1>, dim3(tile_blocks(floats)), dim3(256), 0, (hipStream_t)stream, tiles, dst,
                        g, C, floats);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(KDLAE_EHIP, hipGetErrorString(e));
+  return KDLAE_OK;
+}
+
+extern "C" int kdlae_tile_blend_rates(const float* staged, int R, int B, int C, int H, int W, int tile, int overlap,
+                                      int tile_batch, int scale, float* dst, void* stream) {
+  if (!staged || !dst) return fail(KDLAE_EINVAL_CONFIG, "kdlae_tile_blend_rates: null argument");
+  if (R < 1 || R > 64) return fail(KDLAE_EINVAL_CONFIG, "kdlae_tile_blend_rates: need 1 <= R <= 64");
+  if (B < 1 || C < 1 || tile_batch < 1)
+    return fail(KDLAE_EINVAL_CONFIG, "kdlae_tile_blend_rates: need B, C and tile_batch >= 1");
+  if (scale != 1 && scale != 2) return fail(KDLAE_EINVAL_CONFIG, "kdlae_tile_blend_rates: scale must be 1 or 2");
+  TilePlan p;
+  TRY(make_plan("kdlae_tile_blend_rates", H, W, tile, overlap, p));
+  const long long ntiles = (long long)B * p.ni * p.nj;
+  if (ntiles > INT_MAX || (long long)scale * std::max(H, W) > INT_MAX || (long long)R * B * C > INT_MAX)
+    return fail(KDLAE_EINVAL_SHAPE,
+                "kdlae_tile_blend_rates: more than 2^31 - 1 tiles, images x channels or pixels along an axis");
+  const int s = scale;
+  const TileGeo g{s * H, s * W, s * p.th, s * p.tw, s * p.sy, s * p.sx, p.ni, p.nj};
+  const long long floats = (long long)R * B * C * g.Ly * g.Lx;
+  // a chunk larger than the sweep is one chunk of all the tiles (and keeps k tile_batch inside an int)
+  const int tb = (int)std::min<long long>(tile_batch, ntiles);
+  const bool vec = al16(staged) && al16(dst) && (p.nj == 1 || g.sx % 4 == 0);
+  if (vec)
+    hipLaunchKernelGGL(tile_blend_rates_kernel<4>, dim3(tile_blocks(floats / 4)), dim3(256), 0, (hipStream_t)stream,
+                       staged, dst, g, C, R, B, tb, (int)ntiles, floats / 4);
+  else
+    hipLaunchKernelGGL(tile_blend_rates_kernel<1>, dim3(tile_blocks(floats)), dim3(256), 0, (hipStream_t)stream,
+                       staged, dst, g, C, R, B, tb, (int)ntiles, floats);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(KDLAE_EHIP, hipGetErrorString(e));
   return KDLAE_OK;

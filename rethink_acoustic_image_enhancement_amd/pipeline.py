@@ -11,6 +11,8 @@
   call: R rates of the same images through ``KDLAE_teacher.forward_rates`` (the rate-independent trunk runs
   once), every candidate post-processed as the notebook saves it, and — ``enhance_auto_u8`` — scored by
   ASDQE against the input and the candidate picked per image on the device (``kdlae_rate_select``).
+* ``enhance_rates_tiled_u8`` / ``enhance_auto_tiled_u8`` — the same two calls for images too large for one
+  forward: the sweep runs on tiles (``KDLAE_teacher.forward_rates_tiled``), the blended candidates are scored.
 * ``frames_preprocess_u8`` / ``enhance_frames_u8`` — KDLAE/KDLAE-S.ipynb's cell: F frames (gray or
   cv2 BGR/BGRA u8) -> COLOR_BGR2GRAY -> /255 -> [B,F,H,W] reflect-padded to a multiple of 32 ->
   KDLAE_student -> clamp / crop / permute to [h,w,F] / ``img_as_ubyte``, pre and post on the GPU.
@@ -196,6 +198,77 @@ def enhance_auto_u8(model, scorer, images: torch.Tensor, rates, target=None, sel
     if want_sr:
         with torch.no_grad():
             sr = postprocess_u8(model.forward_sr(hq_sel), h, w, 2, images)
+    out = {"hq": cands[pick], "rate": rt[pick], "index": index, "scores": scores, "sr": sr}
+    torch.cuda.current_stream(dev).synchronize()
+    return out
+
+
+def _sweep_tiled_u8(model, images: torch.Tensor, rates, tile: int, tile_overlap: int, tile_batch: int, bgr: bool,
+                    multiple: int):
+    """-> (rates [R,B], tile plan, hq staging (``kdlae_tile_blend_rates``' layout), blended hq f32 [R,B,C,H,W],
+    candidates u8 [R,B,h,w,C])."""
+    from . import tiling
+    B, h, w, _ = images.shape
+    img, _ = preprocess_u8(images, None, multiple, bgr)
+    rt = _rates_rb(rates, B, images.device)
+    H, W = img.shape[-2:]
+    with torch.no_grad():
+        plan, rt, st_hq, _ = model._sweep_tiles(img, rt, False, tile, tile_overlap, tile_batch)
+    hq = tiling.tile_blend_rates(st_hq, rt.shape[0], B, H, W, tile, tile_overlap, tile_batch, 1)
+    cands = torch.stack([postprocess_u8(hq[r], h, w, 1, images) for r in range(rt.shape[0])])
+    return rt, plan, st_hq, hq, cands
+
+
+def enhance_rates_tiled_u8(model, images: torch.Tensor, rates, tile: int = 512, tile_overlap: int = 32,
+                           tile_batch: int = 16, bgr: bool = False, multiple: int = 8) -> torch.Tensor:
+    """``enhance_tiled_u8``'s hq for every rate of a sweep, for images larger than one forward can hold: u8
+    [B,h,w,C], R rates (scalars or [R,B]) -> u8 [R,B,h,w,C] through ``KDLAE_teacher.forward_rates_tiled``'s
+    sweep.  Candidate r is byte for byte ``enhance_tiled_u8(model, images, rates[r], ...)[0]``."""
+    return _sweep_tiled_u8(model, images, rates, tile, tile_overlap, tile_batch, bgr, multiple)[4]
+
+
+_SCORE_CHUNK_PIXELS = 1 << 22   # pixels of one ASDQE scoring chunk: 64 images up to 256^2, one image from 2048^2
+
+
+def enhance_auto_tiled_u8(model, scorer, images: torch.Tensor, rates, target=None, select: str = "closest",
+                          want_sr: bool = False, tile: int = 512, tile_overlap: int = 32, tile_batch: int = 16,
+                          bgr: bool = False) -> dict:
+    """``enhance_auto_u8`` for images larger than one forward can hold: the sweep runs tiled
+    (``KDLAE_teacher.forward_rates_tiled``), every post-processed full-size candidate — the blended image, not a
+    tile — is scored against its input with ASDQE, and ``kdlae_rate_select`` picks per image.  With ``want_sr``
+    the sr head runs on the staged, unclamped hq tiles of each image's chosen rate only (never on R times the
+    tiles), ``tile_batch`` at a time, and is blended at scale 2.  ``hq`` and ``sr`` equal byte for byte
+    ``enhance_tiled_u8`` called with the per-image chosen rates.  Returns ``enhance_auto_u8``'s dict; one
+    synchronisation, before the results are returned."""
+    from . import tiling
+    if select not in _SELECT_MODES:
+        raise RuntimeError(f"select must be one of {sorted(_SELECT_MODES)}, got {select!r}")
+    B, h, w, _ = images.shape
+    dev = images.device
+    rt, plan, st_hq, hq, cands = _sweep_tiled_u8(model, images, rates, tile, tile_overlap, tile_batch, bgr, 8)
+    R = rt.shape[0]
+    H, W = hq.shape[-2:]
+    scores = torch.empty((R, B), device=dev, dtype=torch.float32)
+    chunk = max(1, min(64, _SCORE_CHUNK_PIXELS // (h * w)))   # asdqe_scores' 64, lowered for large images
+    with torch.no_grad():
+        for c0 in range(0, B, chunk):   # every pair is scored independently
+            lq = to_tensor_u8(images[c0:c0 + chunk])
+            for r in range(R):
+                scores[r, c0:c0 + chunk] = scorer(lq, to_tensor_u8(cands[r, c0:c0 + chunk])).view(-1)
+    index, _ = rate_select(scores, hq, select, target)
+    pick = (index.long(), torch.arange(B, device=dev))
+    sr = None
+    if want_sr:
+        n = B * plan.ni * plan.nj
+        tb = min(int(tile_batch), n)
+        C = hq.shape[2]
+        slot = tiling.staged_slots(index, plan.ni * plan.nj, R, tile_batch)
+        chosen = st_hq.view(n * R, C, plan.th, plan.tw).index_select(0, slot)
+        st_sr = torch.empty((n, C, 2 * plan.th, 2 * plan.tw), device=dev, dtype=torch.float32)
+        with torch.no_grad():
+            for first in range(0, n, tb):
+                st_sr[first:first + tb] = model.forward_sr(chosen[first:first + tb])
+        sr = postprocess_u8(tiling.tile_blend(st_sr, B, H, W, tile, tile_overlap, 2), h, w, 2, images)
     out = {"hq": cands[pick], "rate": rt[pick], "index": index, "scores": scores, "sr": sr}
     torch.cuda.current_stream(dev).synchronize()
     return out

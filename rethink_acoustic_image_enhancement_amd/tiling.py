@@ -2,7 +2,8 @@
 
 Thin wrappers of ``kdlae_tile_plan`` / ``kdlae_tile_gather`` / ``kdlae_tile_blend`` (include/kdlae.h states the
 semantics) on the current stream.  ``KDLAE_teacher.forward_tiled`` and ``pipeline.enhance_tiled_u8`` are built
-on them.  The plan follows upstream Restormer's demo (``--tile`` / ``--tile_overlap``): starts
+on them; ``tile_blend_rates`` (``kdlae_tile_blend_rates``) is the blend of the tiled rate sweep
+(``KDLAE_teacher.forward_rates_tiled``, ``pipeline.enhance_auto_tiled_u8``).  The plan follows upstream Restormer's demo (``--tile`` / ``--tile_overlap``): starts
 ``range(0, L - t, t - tile_overlap) + [L - t]`` per axis, a plain sum over the covering tiles in tile order and
 a division by their count; the tile is clamped per axis (``th = min(tile, H)``, ``tw = min(tile, W)``).
 
@@ -95,4 +96,49 @@ def tile_blend(tiles: torch.Tensor, B: int, H: int, W: int, tile: int = 512, til
                                      int(tile_overlap), int(scale), ctypes.c_void_p(out.data_ptr()),
                                      _stream(tiles.device))
     _lib.check(rc, "kdlae_tile_blend")
+    return out
+
+
+def staged_slots(index: torch.Tensor, tiles_per_image: int, R: int, tile_batch: int) -> torch.Tensor:
+    """Where a tiled rate sweep staged each tile at its image's rate ``index[b]`` (device, integer [B]): for tile
+    ``t`` of the ``n = B tiles_per_image`` the position, in tiles, inside ``kdlae_tile_blend_rates``' chunk-major
+    buffer: chunk ``k = t // tile_batch`` starts at ``k tile_batch R`` and holds rate ``r``, tile ``q = t - k
+    tile_batch`` at ``r count_k + q``.  int64 [n] on the device, no host synchronisation."""
+    n = index.shape[0] * int(tiles_per_image)
+    tb = min(int(tile_batch), n)
+    t = torch.arange(n, device=index.device)
+    k = t // tb
+    count_k = (n - k * tb).clamp(max=tb)
+    return k * tb * int(R) + index.long()[t // int(tiles_per_image)] * count_k + (t - k * tb)
+
+
+def tile_blend_rates(staged: torch.Tensor, R: int, B: int, H: int, W: int, tile: int = 512, tile_overlap: int = 32,
+                     tile_batch: int = 16, scale: int = 1, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``kdlae_tile_blend_rates``: the chunk-major staging of a tiled rate sweep (``kdlae_t_forward_rates`` on the
+    ``n = B ni nj`` tiles ``tile_batch`` at a time; include/kdlae.h states the layout) -> ``[R, B, C, scale H,
+    scale W]`` in one launch; ``out[r]`` has the bits ``tile_blend`` gives for the r-th slice.  ``staged``: a
+    contiguous cuda float32 tensor of any shape with ``n R C scale^2 th tw`` elements (``C`` follows from that)."""
+    if staged.device.type != "cuda" or staged.dtype != torch.float32 or not staged.is_contiguous():
+        raise RuntimeError(f"tile_blend_rates expects a contiguous cuda float32 tensor, got {staged.dtype} "
+                           f"{tuple(staged.shape)} on {staged.device}")
+    p = tile_plan(H, W, tile, tile_overlap)
+    R, B, scale = int(R), int(B), int(scale)
+    if not 1 <= R <= 64 or B < 1 or int(tile_batch) < 1 or scale not in (1, 2):
+        raise RuntimeError(f"tile_blend_rates: need 1 <= R <= 64, B >= 1, tile_batch >= 1 and a scale of 1 or 2, got "
+                           f"R {R}, B {B}, tile_batch {tile_batch}, scale {scale}")
+    per_c = B * p.ni * p.nj * R * scale * scale * p.th * p.tw   # floats per channel
+    C = staged.numel() // per_c
+    if C < 1 or staged.numel() != per_c * C:
+        raise RuntimeError(f"tile_blend_rates: expected {per_c} floats per channel ({B * p.ni * p.nj} tiles, {R} "
+                           f"rates), got {staged.numel()}")
+    shape = (R, B, C, scale * H, scale * W)
+    if out is None:
+        out = torch.empty(shape, device=staged.device, dtype=torch.float32)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != staged.device or \
+            not out.is_contiguous():
+        raise RuntimeError(f"tile_blend_rates: out must be a contiguous float32 {shape} on {staged.device}")
+    rc = _lib.lib().kdlae_tile_blend_rates(ctypes.c_void_p(staged.data_ptr()), R, B, C, int(H), int(W), int(tile),
+                                           int(tile_overlap), int(tile_batch), scale,
+                                           ctypes.c_void_p(out.data_ptr()), _stream(staged.device))
+    _lib.check(rc, "kdlae_tile_blend_rates")
     return out
