@@ -239,6 +239,22 @@ int kdlae_tile_blend(const float* tiles, int B, int C, int H, int W, int tile, i
 int kdlae_tile_blend_rates(const float* staged, int R, int B, int C, int H, int W, int tile, int overlap,
                            int tile_batch, int scale, float* dst, void* stream);
 
+/* The two blends with a separable window that falls towards the tile edge, so that a tile fades out where its
+ * neighbour fades in.  Same arguments, plan, tile order and alignment rule as kdlae_tile_blend /
+ * kdlae_tile_blend_rates, plus two device tables wy [scale th] and wx [scale tw], indexed by the tile-local
+ * coordinate of the (scaled) output pixel.  Per output pixel, over the covering tiles in ascending flat index:
+ *   w = fl(wy[yt] wx[xt]);  E = fl(E + fl(w o));  S = fl(S + w);  cnt = cnt + 1
+ *   out = cnt == 1 ? o : E / S                                  (fp32, no fused multiply-add, true division)
+ * A pixel under exactly one tile takes that tile's value untouched (fl(fl(w o) / w) != o for about one fp32 o in
+ * ten), so tile interiors and a one-tile image keep the tile's bits.  With tables of ones the result has the bits
+ * of the uniform entries (but for a lone -0, which stays -0 here).  16-byte accesses also need wx on 16 bytes; 4-byte accesses otherwise.
+ * Precondition (the entries cannot inspect device values): every table entry is finite and greater than 0.
+ * A null wy or wx is KDLAE_EINVAL_CONFIG; every other refusal as for the uniform entries, all before any launch. */
+int kdlae_tile_blend_w(const float* tiles, int B, int C, int H, int W, int tile, int overlap, int scale,
+                       const float* wy, const float* wx, float* dst, void* stream);
+int kdlae_tile_blend_rates_w(const float* staged, int R, int B, int C, int H, int W, int tile, int overlap,
+                             int tile_batch, int scale, const float* wy, const float* wx, float* dst, void* stream);
+
 /* Measurement hook for bench.py (no effect on results).  When a probe class is armed, every
  * launch of that kernel class inside kdlae_t_forward is bracketed by a pair of HIP events on
  * `stream`; kdlae_t_probe_read synchronises those events and returns the summed device time (ms),

@@ -412,7 +412,7 @@ class KDLAE_teacher(nn.Module):
         return {"hq": hq, "sr": sr}
 
     # ------------------------------------------------------------------ tiled inference
-    def forward_tiled(self, input, tile=512, tile_overlap=32, tile_batch=16):
+    def forward_tiled(self, input, tile=512, tile_overlap=32, tile_batch=16, window="uniform"):
         """``forward`` for images larger than one forward can hold: overlapping ``tile`` x ``tile`` tiles (clamped
         per axis to the image), ``tile_overlap`` pixels shared by neighbours, every covered pixel the plain mean of
         its tiles' outputs (tiling.py and include/kdlae.h state the plan and the sum order; it is upstream
@@ -424,12 +424,18 @@ class KDLAE_teacher(nn.Module):
         gives for that tile alone, for every ``tile_batch``; with one tile per image the result equals ``forward``.
         MDTA's channel attention is global over the pixels it is given, so with more than one tile the result is a
         different function of the image from the untiled ``forward`` (as upstream), not an approximation of it
-        that carries a bound.  Inference only (eval mode, no autograd graph)."""
+        that carries a bound.  Inference only (eval mode, no autograd graph).
+
+        ``window``: ``"uniform"`` (the plain mean above, the default), ``"ramp"``, ``"hann"`` or a pair of per-axis
+        tables (``tiling.tile_window``): a weighted mean whose weights fall towards the tile edge, so that
+        neighbouring tiles cross-fade over their overlap instead of meeting in two steps; a pixel under one tile
+        keeps that tile's value bit for bit."""
         self._check_inference_input(input["img"], "forward_tiled")
         with torch.no_grad():
-            return self._forward_tiled(input["img"], input.get("denoise_rate"), tile, tile_overlap, tile_batch)
+            return self._forward_tiled(input["img"], input.get("denoise_rate"), tile, tile_overlap, tile_batch,
+                                       window=window)
 
-    def _forward_tiled(self, img, rate, tile, tile_overlap, tile_batch, flat=None):
+    def _forward_tiled(self, img, rate, tile, tile_overlap, tile_batch, flat=None, window="uniform"):
         """``flat``: as in ``_forward_eager`` (a trainer's flat parameters; always launched one by one)."""
         from . import tiling
         ci, oc = self._cfg["inp_channels"], self._cfg["out_channels"]
@@ -439,6 +445,10 @@ class KDLAE_teacher(nn.Module):
         if int(tile_batch) < 1:
             raise RuntimeError(f"tile_batch must be at least 1, got {tile_batch}")
         plan = tiling.tile_plan(H, W, tile, tile_overlap)   # refuses a bad shape / tile / overlap before any launch
+        has_sr = self.static == "train"
+        # the blend tables, once per call and before the staging is allocated: a bad window is refused here
+        win_hq = tiling.tile_window(window, H, W, tile, tile_overlap, 1, img.device)
+        win_sr = tiling.tile_window(window, H, W, tile, tile_overlap, 2, img.device) if has_sr else None
         cat = self._cfg["params"] == "cat"
         if cat and (rate is None or tuple(rate.shape) != (B, 1, H, W)):
             raise RuntimeError(f"denoise_rate must be [B,1,H,W]={B, 1, H, W}, got "
@@ -448,7 +458,6 @@ class KDLAE_teacher(nn.Module):
         rate_c = rate.detach().to(device=dev, dtype=torch.float32).contiguous() if cat else None
         n = B * plan.ni * plan.nj
         th, tw = plan.th, plan.tw
-        has_sr = self.static == "train"
         st_hq = torch.empty((n, oc, th, tw), device=dev, dtype=torch.float32)
         st_sr = torch.empty((n, oc, 2 * th, 2 * tw), device=dev, dtype=torch.float32) if has_sr else None
         graphed = flat is None and self.hip_graphs and not torch.cuda.is_current_stream_capturing()
@@ -461,8 +470,8 @@ class KDLAE_teacher(nn.Module):
                 self._forward_graphed(t_img, t_rate, out=out)
             else:
                 self._forward_eager(t_img, t_rate, flat=flat, out=out)
-        hq = tiling.tile_blend(st_hq, B, H, W, tile, tile_overlap, 1)
-        sr = tiling.tile_blend(st_sr, B, H, W, tile, tile_overlap, 2) if has_sr else None
+        hq = tiling.tile_blend(st_hq, B, H, W, tile, tile_overlap, 1, window=win_hq)
+        sr = tiling.tile_blend(st_sr, B, H, W, tile, tile_overlap, 2, window=win_sr) if has_sr else None
         return {"hq": hq, "sr": sr}
 
     # ------------------------------------------------------------------ rate sweep
@@ -529,7 +538,7 @@ class KDLAE_teacher(nn.Module):
         return {"hq": hq, "sr": srt}
 
     # ------------------------------------------------------------------ tiled rate sweep
-    def forward_rates_tiled(self, img, rates, sr=False, tile=512, tile_overlap=32, tile_batch=16):
+    def forward_rates_tiled(self, img, rates, sr=False, tile=512, tile_overlap=32, tile_batch=16, window="uniform"):
         """``forward_rates`` for images larger than one forward can hold: the tiles of ``forward_tiled``'s plan go
         through ``kdlae_t_forward_rates`` ``tile_batch`` at a time (the trunk runs once per tile, the rate tail at
         batch R * count), every chunk writes its block of a chunk-major staging buffer, and one
@@ -539,14 +548,16 @@ class KDLAE_teacher(nn.Module):
         ``{"hq": [R,B,C,H,W], "sr": [R,B,C,2H,2W] or None}``; ``hq[r]`` / ``sr[r]`` are bit for bit what
         ``forward_tiled`` gives with ``denoise_rate = rates[r]`` as a map, for every ``tile_batch``.  The staging
         holds R outputs of every tile (R * B * ni * nj tiles of C * th * tw floats, five times that with ``sr``).
-        Eval mode, eager (no HIP-graph replay), no autograd graph."""
+        Eval mode, eager (no HIP-graph replay), no autograd graph.  ``window``: as in ``forward_tiled``, for both
+        blends."""
         with torch.no_grad():
             plan, rt, st_hq, st_sr = self._sweep_tiles(img, rates, sr, tile, tile_overlap, tile_batch)
             from . import tiling
             B, _, H, W = img.shape
             R = rt.shape[0]
-            hq = tiling.tile_blend_rates(st_hq, R, B, H, W, tile, tile_overlap, tile_batch, 1)
-            srt = tiling.tile_blend_rates(st_sr, R, B, H, W, tile, tile_overlap, tile_batch, 2) if sr else None
+            hq = tiling.tile_blend_rates(st_hq, R, B, H, W, tile, tile_overlap, tile_batch, 1, window=window)
+            srt = tiling.tile_blend_rates(st_sr, R, B, H, W, tile, tile_overlap, tile_batch, 2, window=window) \
+                if sr else None
         return {"hq": hq, "sr": srt}
 
     def _sweep_tiles(self, img, rates, sr, tile, tile_overlap, tile_batch):
@@ -741,12 +752,12 @@ class Restormer(KDLAE_teacher):
             return self._forward_graphed(x, None)["hq"]
         return self._forward_eager(x, None)["hq"]
 
-    def forward_tiled(self, inp_img, tile=512, tile_overlap=32, tile_batch=16):
+    def forward_tiled(self, inp_img, tile=512, tile_overlap=32, tile_batch=16, window="uniform"):
         """``forward`` over overlapping tiles blended on the device (upstream Restormer's ``--tile`` /
-        ``--tile_overlap``; ``KDLAE_teacher.forward_tiled`` states the plan): ``[B,C,H,W] -> [B,C,H,W]``."""
+        ``--tile_overlap``; ``KDLAE_teacher.forward_tiled`` states the plan and ``window``): ``[B,C,H,W] -> [B,C,H,W]``."""
         self._check_inference_input(inp_img, "forward_tiled")
         with torch.no_grad():
-            return self._forward_tiled(inp_img, None, tile, tile_overlap, tile_batch)["hq"]
+            return self._forward_tiled(inp_img, None, tile, tile_overlap, tile_batch, window=window)["hq"]
 
     def forward_rates(self, *args, **kwargs):
         raise RuntimeError("Restormer has no denoise_rate input: forward_rates is KDLAE_teacher's")

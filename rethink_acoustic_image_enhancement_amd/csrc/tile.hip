@@ -16,6 +16,8 @@
 //                       n - k tile_batch) tiles) at float k tile_batch R T, rate r / tile q inside it at
 //                       (r count_k + q) T, T = C s^2 th tw.  Same cover loop, same sum order, same division, so
 //                       dst[r] has the bits tile_blend_kernel gives for the r-th slice laid out [n][C][sth][stw].
+//   tile_blend_w_kernel the two blends with a separable window (kdlae_tile_blend_w, kdlae_tile_blend_rates_w);
+//                       stated at the kernel.
 //
 // V = 4 (float4 loads and stores) when both base pointers sit on 16 bytes and every tile start along x is a
 // multiple of 4 floats (H, W and tile are multiples of 8, so that is a condition on the stride alone); V = 1
@@ -172,6 +174,80 @@ __global__ __launch_bounds__(256) void tile_blend_rates_kernel(const float* __re
   }
 }
 
+// The weighted blends (kdlae_tile_blend_w, kdlae_tile_blend_rates_w): the cover loop, the tile order and the
+// item layout of the two kernels above, with a separable window w = wy[yt] * wx[xt] read at the tile-local
+// coordinate (tables of scale * th and scale * tw floats, every entry finite and > 0).  Per pixel, over the
+// covering tiles in ascending flat index:  w = fl(wy wx);  E = fl(E + fl(w o));  S = fl(S + w);  out = E / S,
+// every operation rounded on its own (no contraction), and a pixel under exactly one tile takes that tile's
+// value untouched: fl(fl(w o) / w) is not o for every o, and tile interiors keep the bits of the tile.
+// RATES selects the chunk-major staging of the rate sweep (tile_blend_rates_kernel's addressing).  V = 4 also
+// needs wx on 16 bytes; the four pixels of a thread share the cover set and wy, each has its own wx.
+template <int V, bool RATES>
+__global__ __launch_bounds__(256) void tile_blend_w_kernel(const float* __restrict__ tiles,
+                                                           const float* __restrict__ wy,
+                                                           const float* __restrict__ wx, float* __restrict__ dst,
+                                                           TileGeo g, int C, int R, int B, int tile_batch,
+                                                           int ntiles, long long total) {
+#pragma clang fp contract(off)
+  const int wq = g.Lx / V;
+  const long long T = (long long)C * g.ty * g.tx;  // floats of one tile
+  for (long long idx = blockIdx.x * 256LL + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
+    const long long row = idx / wq;  // over [R] B C Ly
+    const int X = (int)(idx - row * wq) * V;
+    const int Y = (int)(row % g.Ly);
+    const long long rbc = row / g.Ly;
+    const int c = (int)(rbc % C);
+    const int rb = (int)(rbc / C);
+    const int b = RATES ? rb % B : rb, r = RATES ? rb / B : 0;
+    const Cover cy = tile_cover(Y, g.Ly, g.ty, g.sy, g.ni), cx = tile_cover(X, g.Lx, g.tx, g.sx, g.nj);
+    float E[V], S[V], o[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) E[e] = 0.f, S[e] = 0.f, o[e] = 0.f;
+    int cnt = 0;
+    for (int ii = cy.lo; ii <= cy.hi + cy.last; ++ii) {
+      const int i = ii <= cy.hi ? ii : g.ni - 1;
+      const int yt = Y - (ii <= cy.hi ? i * g.sy : g.Ly - g.ty);
+      const float wr = wy[yt];
+      for (int jj = cx.lo; jj <= cx.hi + cx.last; ++jj) {
+        const int j = jj <= cx.hi ? jj : g.nj - 1;
+        const int xt = X - (jj <= cx.hi ? j * g.sx : g.Lx - g.tx);
+        const int flat = (b * g.ni + i) * g.nj + j;
+        long long slot = flat;
+        if constexpr (RATES) {
+          const int k = flat / tile_batch, q = flat - k * tile_batch;
+          const int cnt_k = min(tile_batch, ntiles - k * tile_batch);
+          slot = (long long)k * tile_batch * R + (long long)r * cnt_k + q;
+        }
+        const float* __restrict__ t = tiles + slot * T + ((long long)c * g.ty + yt) * g.tx + xt;
+        float wc[V];
+        if constexpr (V == 4) {
+          const float4 v = *reinterpret_cast<const float4*>(t);
+          const float4 u = *reinterpret_cast<const float4*>(wx + xt);
+          o[0] = v.x, o[1] = v.y, o[2] = v.z, o[3] = v.w;
+          wc[0] = u.x, wc[1] = u.y, wc[2] = u.z, wc[3] = u.w;
+        } else {
+          o[0] = *t;
+          wc[0] = wx[xt];
+        }
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+          const float w = wr * wc[e];
+          const float wo = w * o[e];
+          E[e] = E[e] + wo;
+          S[e] = S[e] + w;
+        }
+        ++cnt;
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < V; ++e) o[e] = cnt == 1 ? o[e] : E[e] / S[e];
+    if constexpr (V == 4)
+      reinterpret_cast<float4*>(dst)[idx] = make_float4(o[0], o[1], o[2], o[3]);
+    else
+      dst[idx] = o[0];
+  }
+}
+
 static int axis_tiles(int L, int t, int stride) { return L == t ? 1 : (int)ceil_div(L - t, stride) + 1; }
 
 // the argument checks every entry shares; `who` names the entry in the message
@@ -285,4 +361,71 @@ extern "C" int kdlae_tile_blend_rates(const float* staged, int R, int B, int C, 
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(KDLAE_EHIP, hipGetErrorString(e));
   return KDLAE_OK;
+}
+
+// both weighted entries after their checks: R = 0 marks the plain layout [B ni nj][C][s th][s tw]
+static int launch_blend_w(const float* tiles, int R, int B, int C, const TileGeo& g, int nj, int tile_batch,
+                          int ntiles, const float* wy, const float* wx, float* dst, void* stream) {
+  const long long floats = (long long)std::max(R, 1) * B * C * g.Ly * g.Lx;
+  const bool vec = al16(tiles) && al16(dst) && al16(wx) && (nj == 1 || g.sx % 4 == 0);
+  const long long total = vec ? floats / 4 : floats;
+  const dim3 grid(tile_blocks(total)), block(256);
+  const hipStream_t st = (hipStream_t)stream;
+  if (R == 0) {
+    if (vec)
+      hipLaunchKernelGGL((tile_blend_w_kernel<4, false>), grid, block, 0, st, tiles, wy, wx, dst, g, C, 1, B, 1,
+                         ntiles, total);
+    else
+      hipLaunchKernelGGL((tile_blend_w_kernel<1, false>), grid, block, 0, st, tiles, wy, wx, dst, g, C, 1, B, 1,
+                         ntiles, total);
+  } else {
+    if (vec)
+      hipLaunchKernelGGL((tile_blend_w_kernel<4, true>), grid, block, 0, st, tiles, wy, wx, dst, g, C, R, B,
+                         tile_batch, ntiles, total);
+    else
+      hipLaunchKernelGGL((tile_blend_w_kernel<1, true>), grid, block, 0, st, tiles, wy, wx, dst, g, C, R, B,
+                         tile_batch, ntiles, total);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(KDLAE_EHIP, hipGetErrorString(e));
+  return KDLAE_OK;
+}
+
+extern "C" int kdlae_tile_blend_w(const float* tiles, int B, int C, int H, int W, int tile, int overlap, int scale,
+                                  const float* wy, const float* wx, float* dst, void* stream) {
+  if (!tiles || !dst) return fail(KDLAE_EINVAL_CONFIG, "kdlae_tile_blend_w: null argument");
+  if (!wy || !wx) return fail(KDLAE_EINVAL_CONFIG, "kdlae_tile_blend_w: null window table");
+  if (B < 1 || C < 1) return fail(KDLAE_EINVAL_CONFIG, "kdlae_tile_blend_w: need B >= 1 and C >= 1");
+  if (scale != 1 && scale != 2) return fail(KDLAE_EINVAL_CONFIG, "kdlae_tile_blend_w: scale must be 1 or 2");
+  TilePlan p;
+  TRY(make_plan("kdlae_tile_blend_w", H, W, tile, overlap, p));
+  const long long ntiles = (long long)B * p.ni * p.nj;
+  if (ntiles > INT_MAX || (long long)scale * std::max(H, W) > INT_MAX || (long long)B * C > INT_MAX)
+    return fail(KDLAE_EINVAL_SHAPE,
+                "kdlae_tile_blend_w: more than 2^31 - 1 tiles, images x channels or pixels along an axis");
+  const int s = scale;
+  const TileGeo g{s * H, s * W, s * p.th, s * p.tw, s * p.sy, s * p.sx, p.ni, p.nj};
+  return launch_blend_w(tiles, 0, B, C, g, p.nj, 1, (int)ntiles, wy, wx, dst, stream);
+}
+
+extern "C" int kdlae_tile_blend_rates_w(const float* staged, int R, int B, int C, int H, int W, int tile, int overlap,
+                                        int tile_batch, int scale, const float* wy, const float* wx, float* dst,
+                                        void* stream) {
+  if (!staged || !dst) return fail(KDLAE_EINVAL_CONFIG, "kdlae_tile_blend_rates_w: null argument");
+  if (!wy || !wx) return fail(KDLAE_EINVAL_CONFIG, "kdlae_tile_blend_rates_w: null window table");
+  if (R < 1 || R > 64) return fail(KDLAE_EINVAL_CONFIG, "kdlae_tile_blend_rates_w: need 1 <= R <= 64");
+  if (B < 1 || C < 1 || tile_batch < 1)
+    return fail(KDLAE_EINVAL_CONFIG, "kdlae_tile_blend_rates_w: need B, C and tile_batch >= 1");
+  if (scale != 1 && scale != 2) return fail(KDLAE_EINVAL_CONFIG, "kdlae_tile_blend_rates_w: scale must be 1 or 2");
+  TilePlan p;
+  TRY(make_plan("kdlae_tile_blend_rates_w", H, W, tile, overlap, p));
+  const long long ntiles = (long long)B * p.ni * p.nj;
+  if (ntiles > INT_MAX || (long long)scale * std::max(H, W) > INT_MAX || (long long)R * B * C > INT_MAX)
+    return fail(KDLAE_EINVAL_SHAPE,
+                "kdlae_tile_blend_rates_w: more than 2^31 - 1 tiles, images x channels or pixels along an axis");
+  const int s = scale;
+  const TileGeo g{s * H, s * W, s * p.th, s * p.tw, s * p.sy, s * p.sx, p.ni, p.nj};
+  // a chunk larger than the sweep is one chunk of all the tiles (and keeps k tile_batch inside an int)
+  const int tb = (int)std::min<long long>(tile_batch, ntiles);
+  return launch_blend_w(staged, R, B, C, g, p.nj, tb, (int)ntiles, wy, wx, dst, stream);
 }

@@ -98,18 +98,19 @@ def enhance_u8(model, images: torch.Tensor, denoise_rate, bgr: bool = False, mul
 
 
 def enhance_tiled_u8(model, images: torch.Tensor, denoise_rate, tile: int = 512, tile_overlap: int = 32,
-                     tile_batch: int = 16, bgr: bool = False, multiple: int = 8):
+                     tile_batch: int = 16, bgr: bool = False, multiple: int = 8, window="uniform"):
     """``enhance_u8`` for images larger than one forward can hold: the same pre- and post-processing around
     ``KDLAE_teacher.forward_tiled`` (overlapping tiles blended on the device) -> (hq u8, sr u8 or None).  A tiled
     result is a different function of the image from ``enhance_u8``'s (MDTA's channel attention is global over
     the pixels of each tile), as it is in upstream Restormer's tiled demo; it equals it when one tile covers
-    the padded image."""
+    the padded image.  ``window``: the blend window, as ``KDLAE_teacher.forward_tiled`` takes it."""
     B, h, w, C = images.shape
     if _is_restormer(model):
         img, _ = preprocess_u8(images, None, multiple, bgr)
-        return postprocess_u8(model.forward_tiled(img, tile, tile_overlap, tile_batch), h, w, 1, images), None
+        return postprocess_u8(model.forward_tiled(img, tile, tile_overlap, tile_batch, window), h, w, 1,
+                              images), None
     img, rmap = preprocess_u8(images, denoise_rate, multiple, bgr)
-    pred = model.forward_tiled({"img": img, "denoise_rate": rmap}, tile, tile_overlap, tile_batch)
+    pred = model.forward_tiled({"img": img, "denoise_rate": rmap}, tile, tile_overlap, tile_batch, window)
     hq = postprocess_u8(pred["hq"], h, w, 1, images)
     sr = postprocess_u8(pred["sr"], h, w, 2, images) if pred.get("sr") is not None else None
     return hq, sr
@@ -204,7 +205,7 @@ def enhance_auto_u8(model, scorer, images: torch.Tensor, rates, target=None, sel
 
 
 def _sweep_tiled_u8(model, images: torch.Tensor, rates, tile: int, tile_overlap: int, tile_batch: int, bgr: bool,
-                    multiple: int):
+                    multiple: int, window="uniform"):
     """-> (rates [R,B], tile plan, hq staging (``kdlae_tile_blend_rates``' layout), blended hq f32 [R,B,C,H,W],
     candidates u8 [R,B,h,w,C])."""
     from . import tiling
@@ -214,17 +215,19 @@ def _sweep_tiled_u8(model, images: torch.Tensor, rates, tile: int, tile_overlap:
     H, W = img.shape[-2:]
     with torch.no_grad():
         plan, rt, st_hq, _ = model._sweep_tiles(img, rt, False, tile, tile_overlap, tile_batch)
-    hq = tiling.tile_blend_rates(st_hq, rt.shape[0], B, H, W, tile, tile_overlap, tile_batch, 1)
+    hq = tiling.tile_blend_rates(st_hq, rt.shape[0], B, H, W, tile, tile_overlap, tile_batch, 1, window=window)
     cands = torch.stack([postprocess_u8(hq[r], h, w, 1, images) for r in range(rt.shape[0])])
     return rt, plan, st_hq, hq, cands
 
 
 def enhance_rates_tiled_u8(model, images: torch.Tensor, rates, tile: int = 512, tile_overlap: int = 32,
-                           tile_batch: int = 16, bgr: bool = False, multiple: int = 8) -> torch.Tensor:
+                           tile_batch: int = 16, bgr: bool = False, multiple: int = 8,
+                           window="uniform") -> torch.Tensor:
     """``enhance_tiled_u8``'s hq for every rate of a sweep, for images larger than one forward can hold: u8
     [B,h,w,C], R rates (scalars or [R,B]) -> u8 [R,B,h,w,C] through ``KDLAE_teacher.forward_rates_tiled``'s
-    sweep.  Candidate r is byte for byte ``enhance_tiled_u8(model, images, rates[r], ...)[0]``."""
-    return _sweep_tiled_u8(model, images, rates, tile, tile_overlap, tile_batch, bgr, multiple)[4]
+    sweep.  Candidate r is byte for byte ``enhance_tiled_u8(model, images, rates[r], ...)[0]`` with the same
+    ``window``."""
+    return _sweep_tiled_u8(model, images, rates, tile, tile_overlap, tile_batch, bgr, multiple, window)[4]
 
 
 _SCORE_CHUNK_PIXELS = 1 << 22   # pixels of one ASDQE scoring chunk: 64 images up to 256^2, one image from 2048^2
@@ -232,20 +235,22 @@ _SCORE_CHUNK_PIXELS = 1 << 22   # pixels of one ASDQE scoring chunk: 64 images u
 
 def enhance_auto_tiled_u8(model, scorer, images: torch.Tensor, rates, target=None, select: str = "closest",
                           want_sr: bool = False, tile: int = 512, tile_overlap: int = 32, tile_batch: int = 16,
-                          bgr: bool = False) -> dict:
+                          bgr: bool = False, window="uniform") -> dict:
     """``enhance_auto_u8`` for images larger than one forward can hold: the sweep runs tiled
     (``KDLAE_teacher.forward_rates_tiled``), every post-processed full-size candidate — the blended image, not a
     tile — is scored against its input with ASDQE, and ``kdlae_rate_select`` picks per image.  With ``want_sr``
     the sr head runs on the staged, unclamped hq tiles of each image's chosen rate only (never on R times the
     tiles), ``tile_batch`` at a time, and is blended at scale 2.  ``hq`` and ``sr`` equal byte for byte
-    ``enhance_tiled_u8`` called with the per-image chosen rates.  Returns ``enhance_auto_u8``'s dict; one
+    ``enhance_tiled_u8`` called with the per-image chosen rates and the same ``window`` (it shapes both blends,
+    so also the candidates that are scored).  Returns ``enhance_auto_u8``'s dict; one
     synchronisation, before the results are returned."""
     from . import tiling
     if select not in _SELECT_MODES:
         raise RuntimeError(f"select must be one of {sorted(_SELECT_MODES)}, got {select!r}")
     B, h, w, _ = images.shape
     dev = images.device
-    rt, plan, st_hq, hq, cands = _sweep_tiled_u8(model, images, rates, tile, tile_overlap, tile_batch, bgr, 8)
+    rt, plan, st_hq, hq, cands = _sweep_tiled_u8(model, images, rates, tile, tile_overlap, tile_batch, bgr, 8,
+                                                 window)
     R = rt.shape[0]
     H, W = hq.shape[-2:]
     scores = torch.empty((R, B), device=dev, dtype=torch.float32)
@@ -268,7 +273,8 @@ def enhance_auto_tiled_u8(model, scorer, images: torch.Tensor, rates, target=Non
         with torch.no_grad():
             for first in range(0, n, tb):
                 st_sr[first:first + tb] = model.forward_sr(chosen[first:first + tb])
-        sr = postprocess_u8(tiling.tile_blend(st_sr, B, H, W, tile, tile_overlap, 2), h, w, 2, images)
+        sr = postprocess_u8(tiling.tile_blend(st_sr, B, H, W, tile, tile_overlap, 2, window=window), h, w, 2,
+                            images)
     out = {"hq": cands[pick], "rate": rt[pick], "index": index, "scores": scores, "sr": sr}
     torch.cuda.current_stream(dev).synchronize()
     return out

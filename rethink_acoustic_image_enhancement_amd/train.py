@@ -1352,7 +1352,7 @@ class _ImageCleanTrainer(_TrainingState):
 
     @torch.no_grad()
     def validate(self, batches, window_size=8, crop_border=0, use_image=False, use_ema=None, metrics=("psnr",),
-                 niqe=False, niqe_params=None, tile=None, tile_overlap=32, tile_batch=16):
+                 niqe=False, niqe_params=None, tile=None, tile_overlap=32, tile_batch=16, tile_window="uniform"):
         """ImageCleanModel.nondist_validation with pad_test (image_restoration_model.py:226-348) over
         ``(lq, gt)`` pairs, ``lq = {'img', 'denoise_rate'}``, ``gt = {'hq', 'sr'}`` (RestormerTrainer: two
         tensors, and only the ``*_hq`` results): reflect-pad ``img`` and the
@@ -1370,7 +1370,8 @@ class _ImageCleanTrainer(_TrainingState):
         (``KDLAE_teacher.forward_tiled``'s tiles, ``tile_overlap`` and ``tile_batch``, with the weights chosen
         below) instead of one ``kdlae_t_forward``; the padded sizes must then be multiples of 8.  A tiled output
         is a different function of the image from the untiled one (MDTA's attention is global over each tile),
-        so its metrics are not comparable digit for digit with ``tile=None``, today's path.
+        so its metrics are not comparable digit for digit with ``tile=None``, today's path.  ``tile_window``:
+        the blend window of the tiled forward (``forward_tiled``'s ``window``); not read without ``tile``.
 
         ``use_ema=None``: the EMA weights when ``ema_decay > 0`` (net_g_ema, :242-248), else the live ones.
         The chosen flat vector is packed straight into the module's inference handle; the trainer's buffers,
@@ -1395,7 +1396,8 @@ class _ImageCleanTrainer(_TrainingState):
             if tile is None:
                 out = self.model._forward_eager(img_p, rate_p, flat=flat)
             else:
-                out = self.model._forward_tiled(img_p, rate_p, tile, tile_overlap, tile_batch, flat=flat)
+                out = self.model._forward_tiled(img_p, rate_p, tile, tile_overlap, tile_batch, flat=flat,
+                                                window=tile_window)
             # the last item's cropped outputs (pad_test's self.output, :236-237), as views
             self.val_output = {"hq": out["hq"][..., :h, :w],
                                "sr": out["sr"][..., :2 * h, :2 * w] if out["sr"] is not None else None}
