@@ -255,6 +255,41 @@ int kdlae_tile_blend_w(const float* tiles, int B, int C, int H, int W, int tile,
 int kdlae_tile_blend_rates_w(const float* staged, int R, int B, int C, int H, int W, int tile, int overlap,
                              int tile_batch, int scale, const float* wy, const float* wx, float* dst, void* stream);
 
+/* Clip inference for KDLAE-S: overlapping windows of `frames` consecutive frames of a clip [B][T][H][W], run
+ * through the student one window at a time and blended on the device.  The tile plan on the frame axis (fixed by
+ * T, frames, overlap; T >= 1, frames >= 1, else KDLAE_EINVAL_CONFIG; 0 <= overlap < f, else KDLAE_EINVAL_SHAPE):
+ *   f = min(frames, T), stride = f - overlap
+ *   starts range(0, T - f, stride) + [T - f]: window i of n starts at i stride for i < n - 1 and at T - f for
+ *   the last; n = ceil((T - f) / stride) + 1, which is 1 when T == f
+ *   window (b, i) has flat index b n + i
+ * The kernels know nothing of the model: any H, W >= 1.  kdlae_clip_plan is host only.  kdlae_clip_gather copies
+ * windows first .. first + count - 1 of src into dense dst [count][f][H][W] (16-byte accesses when both pointers
+ * sit on 16 bytes and H W % 4 == 0, 4-byte accesses otherwise).  kdlae_clip_blend takes windows [B n][f][H][W]
+ * and writes dst [B][T][H][W] (the same access rule).  With wt == NULL, per output element: 0 + o1 + o2 + ... over
+ * the covering windows in ascending index, in fp32, divided by the fp32 count: E[:, s:s+f].add_(y),
+ * W[s:s+f].add_(1), E.div_(W) of the usual host loop, bit for bit (so a lone -0 comes out +0, as it does there).
+ * With a device table wt [f], indexed by the frame's position p inside its window, kdlae_tile_blend_w's rule on
+ * one axis:
+ *   w = wt[p];  E = fl(E + fl(w o));  S = fl(S + w);  cnt = cnt + 1
+ *   out = cnt == 1 ? o : E / S                                  (fp32, no fused multiply-add, true division)
+ * so a frame under exactly one window keeps that window's bits.  Precondition (the entries cannot inspect device
+ * values): every table entry is finite and greater than 0.  One thread per output pixel group loops over its
+ * windows: no atomics, the result is a function of the inputs alone.
+ * kdlae_clip_blend_u8 runs the same blend and applies kdlae_postprocess_u8's rule to the blended value in the
+ * same thread: clamp to [0, 1], rint(x 255), cropped to h <= H, w <= W, written as dst u8 [B][T][h][w] in frame
+ * order: the bytes of kdlae_postprocess_u8 on kdlae_clip_blend's output, with no black-pixel mask, no limit on T
+ * and no float clip in between.  Any byte alignment of dst (4-byte stores when dst sits on 4 bytes, w % 4 == 0,
+ * windows sits on 16 bytes and W % 4 == 0; single bytes otherwise).
+ * Null pointers (wt excepted), B, H, W or count < 1, first < 0, first + count > B n, h or w < 1, h > H, w > W:
+ * KDLAE_EINVAL_CONFIG.  Every check comes before the launch. */
+int kdlae_clip_plan(int T, int frames, int overlap, int* f, int* n, int* stride);
+int kdlae_clip_gather(const float* src, int B, int T, int H, int W, int frames, int overlap, int first, int count,
+                      float* dst, void* stream);
+int kdlae_clip_blend(const float* windows, int B, int T, int H, int W, int frames, int overlap, const float* wt,
+                     float* dst, void* stream);
+int kdlae_clip_blend_u8(const float* windows, int B, int T, int H, int W, int h, int w, int frames, int overlap,
+                        const float* wt, uint8_t* dst, void* stream);
+
 /* Measurement hook for bench.py (no effect on results).  When a probe class is armed, every
  * launch of that kernel class inside kdlae_t_forward is bracketed by a pair of HIP events on
  * `stream`; kdlae_t_probe_read synchronises those events and returns the summed device time (ms),

@@ -828,15 +828,18 @@ class KDLAE_student(nn.Module):
             self._engines[idx] = eng
         return eng
 
-    def forward(self, x):
+    def _check_input(self, x):
         if x.device.type != "cuda":
             raise RuntimeError("KDLAE_student (MI355X build) runs on ROCm devices only; there is no CPU fallback")
         if x.dim() != 4:
             raise RuntimeError(f"expected x [B,F,H,W], got {tuple(x.shape)}")
-        B, Fr, H, W = x.shape
+        H, W = x.shape[-2:]
         m = 1 << self.num_levels
         if H % m or W % m:
             raise RuntimeError(f"KDLAE_student needs H and W divisible by {m}, got {H}x{W}")
+
+    def forward(self, x):
+        self._check_input(x)
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             if self.training and any(p.requires_grad for p in self.parameters()):
                 # BasicSR's KDLAE-S training (KDLAES.yml, l_pix.backward()): the HIP training engine
@@ -856,8 +859,54 @@ class KDLAE_student(nn.Module):
                 self._warned_grad = True
         return self._forward_eager(x)
 
-    def _forward_eager(self, x, flat=None):
-        """``flat``: run with this packed parameter vector (``_Engine.pack_flat``) instead of the module's own."""
+    def forward_clip(self, x, frames=7, overlap=2, window_batch=8, window="uniform"):
+        """``forward`` for a clip of any length: ``x [B,T,H,W] -> [B,T,H,W]`` through overlapping windows of
+        ``frames`` consecutive frames (the network was trained at 7), ``overlap`` frames shared by neighbours, every
+        frame the plain mean of its windows' outputs (clips.py and include/kdlae.h state the plan and the sum
+        order).  Windows are gathered on the device ``window_batch`` at a time and go through this module's own
+        inference forward; the outputs land in a staging tensor in window order and one blend launch writes the
+        result.
+
+        Each window's rows are bit for bit what ``forward`` gives for that window alone at batch 1, for every
+        ``window_batch``, so the result equals the host loop (slice, forward, ``E[:, s:s+f].add_(y)``,
+        ``W[s:s+f].add_(1)``, ``E.div_(W)``) bit for bit; ``T <= frames`` is one window and equals ``forward(x)``.
+        The 3-D convolutions zero-pad along the frame axis, so with more than one window the result is a different
+        function of the clip from ``forward`` over all T frames, not an approximation of it that carries a bound.
+        Inference only (no autograd graph).
+
+        ``window``: ``"uniform"`` (the plain mean, the default), ``"ramp"``, ``"hann"`` or a table of ``f`` weights
+        (``clips.clip_window``): a weighted mean whose weights fall towards the window's ends, where the zero
+        padding is felt, so that neighbouring windows cross-fade over their overlap; a frame under one window
+        keeps that window's value bit for bit."""
+        from . import clips
+        self._check_input(x)
+        B, T, H, W = x.shape
+        if int(window_batch) < 1:
+            raise RuntimeError(f"window_batch must be at least 1, got {window_batch}")
+        plan = clips.clip_plan(T, frames, overlap)   # refuses a bad T / frames / overlap before any launch
+        with torch.no_grad():
+            # the blend table, once per call and before the staging is allocated: a bad window is refused here
+            table = clips.clip_window(window, T, frames, overlap, x.device)
+            return clips.clip_blend(self._clip_windows(x, plan, frames, overlap, window_batch), B, T, frames, overlap,
+                                    table)
+
+    def _clip_windows(self, x, plan, frames, overlap, window_batch):
+        """Every window of ``x``'s plan through ``_forward_eager`` -> the outputs [B n, f, H, W] in window order."""
+        from . import clips
+        B, _, H, W = x.shape
+        x_c = x.detach().to(torch.float32).contiguous()
+        n = B * plan.n
+        staged = torch.empty((n, plan.f, H, W), device=x.device, dtype=torch.float32)
+        for first in range(0, n, int(window_batch)):
+            count = min(int(window_batch), n - first)
+            self._forward_eager(clips.clip_gather(x_c, frames, overlap, first, count),
+                                out=staged[first:first + count])
+        return staged
+
+    def _forward_eager(self, x, flat=None, out=None):
+        """``flat``: run with this packed parameter vector (``_Engine.pack_flat``) instead of the module's own.
+        ``out``: a contiguous fp32 destination of the output's shape to write into instead of a fresh tensor: how
+        ``forward_clip`` fills its staging."""
         B, Fr, H, W = x.shape
         dev = x.device
         stream = torch.cuda.current_stream(dev).cuda_stream
@@ -867,7 +916,8 @@ class KDLAE_student(nn.Module):
         else:
             eng.pack_flat(flat, stream)
         x_c = x.detach().to(torch.float32).contiguous()
-        out = torch.empty((B, Fr, H, W), device=dev, dtype=torch.float32)
+        if out is None:
+            out = torch.empty((B, Fr, H, W), device=dev, dtype=torch.float32)
         L = _lib.lib()
         nbytes = L.kdlae_s_workspace_bytes(eng.handle, B, Fr, H, W)
         if nbytes < 0:

@@ -29,6 +29,7 @@ EXPORTS = (
     "kdlae_rate_select",
     "kdlae_tile_plan", "kdlae_tile_gather", "kdlae_tile_blend", "kdlae_tile_blend_rates",
     "kdlae_tile_blend_w", "kdlae_tile_blend_rates_w",
+    "kdlae_clip_plan", "kdlae_clip_gather", "kdlae_clip_blend", "kdlae_clip_blend_u8",
     "kdlae_t_probe_arm", "kdlae_t_probe_read",
     "kdlae_t_debug_tap_count", "kdlae_t_debug_tap_info", "kdlae_t_debug_taps", "kdlae_t_debug_sr_fold",
     "kdlae_s_create", "kdlae_s_destroy", "kdlae_s_num_params", "kdlae_s_param_info",
@@ -243,6 +244,12 @@ def lib() -> ctypes.CDLL:
                                      c_void_p, c_void_p]
     L.kdlae_tile_blend_rates_w.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                            c_void_p, c_void_p, c_void_p, c_void_p]
+    L.kdlae_clip_plan.argtypes = [c_int, c_int, c_int] + [ctypes.POINTER(c_int)] * 3
+    L.kdlae_clip_gather.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                    c_void_p]
+    L.kdlae_clip_blend.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    L.kdlae_clip_blend_u8.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                      c_void_p, c_void_p]
     L.kdlae_t_probe_arm.argtypes = [c_void_p, c_int, c_int]
     L.kdlae_t_probe_read.argtypes = [c_void_p, ctypes.POINTER(c_double), ctypes.POINTER(c_int64),
                                      ctypes.POINTER(c_double), ctypes.POINTER(c_double)]

@@ -16,6 +16,9 @@
 * ``frames_preprocess_u8`` / ``enhance_frames_u8`` — KDLAE/KDLAE-S.ipynb's cell: F frames (gray or
   cv2 BGR/BGRA u8) -> COLOR_BGR2GRAY -> /255 -> [B,F,H,W] reflect-padded to a multiple of 32 ->
   KDLAE_student -> clamp / crop / permute to [h,w,F] / ``img_as_ubyte``, pre and post on the GPU.
+* ``enhance_clip_u8`` — the same cell for a whole clip of T frames: one ``frames_preprocess_u8``, overlapping
+  windows of ``frames`` frames through KDLAE_student (``forward_clip``'s loop), and one launch that blends the
+  windows and writes the u8 clip in frame order (clips.py).
 * ``asdqe_scores`` / ``score_statistics`` / ``write_statistics_csv`` — ASDQE/ASDQE_test.py's
   ``infer`` + ``calculate_statistics`` + ``visualize_comparison`` CSV (:87-133).
 """
@@ -302,6 +305,28 @@ def enhance_frames_u8(model, frames: torch.Tensor, multiple: int = 32) -> torch.
     with torch.no_grad():
         y = model(x)
     return postprocess_u8(y, h, w, 1, None)
+
+
+def enhance_clip_u8(model, clip: torch.Tensor, frames: int = 7, overlap: int = 2, window_batch: int = 8,
+                    window="uniform", multiple: int = 32) -> torch.Tensor:
+    """``enhance_frames_u8`` for a whole clip: u8 [B,T,h,w] (gray) or [B,T,h,w,C] (cv2 BGR / BGRA) -> u8 [B,T,h,w]
+    in frame order.  One ``frames_preprocess_u8`` over the clip, ``KDLAE_student.forward_clip``'s window loop
+    (``frames``, ``overlap``, ``window_batch``, ``window`` as it takes them), then ``clips.clip_blend_u8``: the
+    blend, the clamp, the crop and ``img_as_ubyte`` in one launch, with no float clip-sized output and no permute.
+    Byte for byte the per-window host loop followed by ``postprocess_u8`` and a permute."""
+    from . import clips
+    if clip.dim() not in (4, 5):
+        raise RuntimeError("enhance_clip_u8 expects a cuda uint8 tensor [B,T,h,w] or [B,T,h,w,C]")
+    B, T, h, w = clip.shape[:4]
+    if int(window_batch) < 1:
+        raise RuntimeError(f"window_batch must be at least 1, got {window_batch}")
+    plan = clips.clip_plan(T, frames, overlap)   # refuses a bad T / frames / overlap before any launch
+    table = clips.clip_window(window, T, frames, overlap, clip.device)   # a bad window is refused here
+    x = frames_preprocess_u8(clip, multiple)
+    model._check_input(x)
+    with torch.no_grad():
+        return clips.clip_blend_u8(model._clip_windows(x, plan, frames, overlap, window_batch), B, T, h, w, frames,
+                                   overlap, table)
 
 
 def to_tensor_u8(images: torch.Tensor) -> torch.Tensor:
