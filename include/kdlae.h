@@ -290,6 +290,47 @@ int kdlae_clip_blend(const float* windows, int B, int T, int H, int W, int frame
 int kdlae_clip_blend_u8(const float* windows, int B, int T, int H, int W, int h, int w, int frames, int overlap,
                         const float* wt, uint8_t* dst, void* stream);
 
+/* Streaming inference for KDLAE-S: B parallel sources deliver one frame at a time and every frame comes back
+ * enhanced at a fixed latency.  The rule (fixed by frames = F >= 1 and emit, 0 <= emit < F; streams.py's default
+ * emit is F / 2).  Frame t of a stream of T frames is
+ *   f = min(F, T);  s_t = min(max(t - emit, 0), T - f);  out[:, t] = forward(x[:, s_t : s_t + f])[:, t - s_t]
+ * so every frame comes from the window in which it sits at position emit, but for the first emit frames (the
+ * first window) and the last F - 1 - emit (the last window); a stream shorter than F is one window.  emit = F - 1
+ * is the causal setting with no latency.  As with the clip entries, the zero padding along the frame axis makes
+ * this a different function of the stream from one forward over all T frames: there is no error bound to state.
+ * The schedule (push t, 0-based, returns nothing while t < F - 1, frames 0 .. emit at t = F - 1, frame
+ * t - (F - 1 - emit) afterwards; the flush returns the rest) lives in streams.py; the entries below keep the
+ * window on the device.
+ *
+ * state: kdlae_stream_state_bytes(B, frames, H, W) bytes of device memory (-1 for sizes < 1): a 16-byte header
+ * whose first 8 bytes are the push counter, then the ring [B][frames][H][W] fp32 of converted frames; frame number
+ * c lives in slot c % frames.  kdlae_stream_reset sets the counter to 0 and leaves the ring as it is: a slot's old
+ * contents are only ever read into stack positions that have no frame yet, which are unspecified until `frames`
+ * pushes have been made and must not be used.
+ * kdlae_stream_push_u8: frame u8 [B][h][w][channels] (channels 1 = gray, 3 / 4 = BGR / BGRA) is converted by
+ * exactly kdlae_frames_preprocess_u8's rule (cv2 COLOR_BGR2GRAY in 8-bit fixed point, / 255, reflect-padded on the
+ * bottom/right to (H, W) = kdlae_padded_size(h, w, multiple)) and, with count the counter's value read on the
+ * device, stored in ring slot count % frames; stack f32 [B][frames][H][W] receives the window in time order:
+ * positions 0 .. frames - 2 from the ring's other slots, oldest first, position frames - 1 the new frame.  One
+ * launch, one thread per pixel group; the slot written is the one whose frame drops out, so no thread reads
+ * what another writes.  The counter is not a launch argument: a captured graph of the launch serves every push.
+ * kdlae_stream_push_f32: the same for a frame f32 [B][H][W] the caller has preprocessed: a bit copy, no padding.
+ * kdlae_stream_advance: count = count + 1, one thread with a plain store, stream-ordered after the launches that
+ * read the counter.  A push without an advance overwrites the same slot again.
+ * Access widths: 16-byte accesses of ring, stack and an fp32 frame when state, stack (and the fp32 frame) sit on
+ * 16 bytes and W % 4 == 0, 4-byte accesses otherwise.  The u8 source may sit at any byte offset and is read one
+ * byte at a time, but for a gray source on 4 bytes with w % 4 == 0 under 16-byte accesses: 4 bytes a load.
+ * Null pointers, B, h, w, H, W or frames < 1, channels outside {1, 3, 4}, multiple < 1: KDLAE_EINVAL_CONFIG.  A
+ * frame smaller than its reflect padding, state off 8 bytes, stack or an fp32 frame off 4 bytes, more than
+ * 2^31 - 1 pixels of a frame or rows of all sources: KDLAE_EINVAL_SHAPE.  Every check comes before the launch. */
+int64_t kdlae_stream_state_bytes(int B, int frames, int H, int W);
+int kdlae_stream_reset(void* state, void* stream);
+int kdlae_stream_push_u8(const uint8_t* frame, int B, int h, int w, int channels, int multiple, int frames,
+                         void* state, float* stack, void* stream);
+int kdlae_stream_push_f32(const float* frame, int B, int H, int W, int frames, void* state, float* stack,
+                          void* stream);
+int kdlae_stream_advance(void* state, void* stream);
+
 /* Measurement hook for bench.py (no effect on results).  When a probe class is armed, every
  * launch of that kernel class inside kdlae_t_forward is bracketed by a pair of HIP events on
  * `stream`; kdlae_t_probe_read synchronises those events and returns the summed device time (ms),

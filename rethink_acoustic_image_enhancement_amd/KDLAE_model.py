@@ -903,6 +903,13 @@ class KDLAE_student(nn.Module):
                                 out=staged[first:first + count])
         return staged
 
+    def stream(self, batch, h, w, frames=7, emit=None, channels=1, multiple=32, dtype="u8"):
+        """A ``streams.StudentStream`` on this module: frames of ``batch`` parallel sources pushed one at a time,
+        every frame returned enhanced from the window in which it sits at position ``emit`` (streams.py states the
+        rule and the schedule), the steady state replayed as one HIP graph."""
+        from .streams import StudentStream
+        return StudentStream(self, batch, h, w, frames, emit, channels, multiple, dtype)
+
     def _forward_eager(self, x, flat=None, out=None):
         """``flat``: run with this packed parameter vector (``_Engine.pack_flat``) instead of the module's own.
         ``out``: a contiguous fp32 destination of the output's shape to write into instead of a fresh tensor: how

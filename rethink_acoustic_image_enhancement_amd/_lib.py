@@ -30,6 +30,8 @@ EXPORTS = (
     "kdlae_tile_plan", "kdlae_tile_gather", "kdlae_tile_blend", "kdlae_tile_blend_rates",
     "kdlae_tile_blend_w", "kdlae_tile_blend_rates_w",
     "kdlae_clip_plan", "kdlae_clip_gather", "kdlae_clip_blend", "kdlae_clip_blend_u8",
+    "kdlae_stream_state_bytes", "kdlae_stream_reset", "kdlae_stream_push_u8", "kdlae_stream_push_f32",
+    "kdlae_stream_advance",
     "kdlae_t_probe_arm", "kdlae_t_probe_read",
     "kdlae_t_debug_tap_count", "kdlae_t_debug_tap_info", "kdlae_t_debug_taps", "kdlae_t_debug_sr_fold",
     "kdlae_s_create", "kdlae_s_destroy", "kdlae_s_num_params", "kdlae_s_param_info",
@@ -250,6 +252,13 @@ def lib() -> ctypes.CDLL:
     L.kdlae_clip_blend.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
     L.kdlae_clip_blend_u8.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                       c_void_p, c_void_p]
+    L.kdlae_stream_state_bytes.argtypes = [c_int, c_int, c_int, c_int]
+    L.kdlae_stream_state_bytes.restype = c_int64
+    L.kdlae_stream_reset.argtypes = [c_void_p, c_void_p]
+    L.kdlae_stream_push_u8.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                       c_void_p]
+    L.kdlae_stream_push_f32.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    L.kdlae_stream_advance.argtypes = [c_void_p, c_void_p]
     L.kdlae_t_probe_arm.argtypes = [c_void_p, c_int, c_int]
     L.kdlae_t_probe_read.argtypes = [c_void_p, ctypes.POINTER(c_double), ctypes.POINTER(c_int64),
                                      ctypes.POINTER(c_double), ctypes.POINTER(c_double)]
@@ -390,7 +399,7 @@ def lib() -> ctypes.CDLL:
     L.kdlae_debug_gemm_variant.argtypes = [c_int, c_int, ctypes.POINTER(c_int)]
     for name in EXPORTS:
         if not name.endswith(("_last_error", "_abi_version", "_workspace_bytes", "_padded_size", "_num_floats",
-                              "_scratch_floats", "_scratch_bytes", "_params_numel", "_mark_lo", "_num_stat_floats",
+                              "_scratch_floats", "_scratch_bytes", "_state_bytes", "_params_numel", "_mark_lo", "_num_stat_floats",
                               "_backward_launches")):
             getattr(L, name).restype = c_int
     _lib = L

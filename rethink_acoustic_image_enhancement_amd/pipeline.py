@@ -19,6 +19,9 @@
 * ``enhance_clip_u8`` — the same cell for a whole clip of T frames: one ``frames_preprocess_u8``, overlapping
   windows of ``frames`` frames through KDLAE_student (``forward_clip``'s loop), and one launch that blends the
   windows and writes the u8 clip in frame order (clips.py).
+* ``enhance_stream_u8`` — the same cell for a source that delivers one frame at a time: a generator over the
+  arriving frames that yields every frame enhanced, in order, at a fixed latency (streams.py: the window lives in
+  a ring on the device and the steady state replays one HIP graph).
 * ``asdqe_scores`` / ``score_statistics`` / ``write_statistics_csv`` — ASDQE/ASDQE_test.py's
   ``infer`` + ``calculate_statistics`` + ``visualize_comparison`` CSV (:87-133).
 """
@@ -327,6 +330,33 @@ def enhance_clip_u8(model, clip: torch.Tensor, frames: int = 7, overlap: int = 2
     with torch.no_grad():
         return clips.clip_blend_u8(model._clip_windows(x, plan, frames, overlap, window_batch), B, T, h, w, frames,
                                    overlap, table)
+
+
+def enhance_stream_u8(model, frames_iter, frames: int = 7, emit: int | None = None, multiple: int = 32):
+    """``enhance_frames_u8`` for a live source: a generator over an iterable of cuda u8 frames ``[B,h,w]`` (gray) or
+    ``[B,h,w,C]`` (cv2 BGR / BGRA) that yields u8 ``[B,h,w]`` frames in order, each from the window of ``frames``
+    frames in which it sits at position ``emit`` (default ``frames // 2``; streams.py states the rule), with the
+    flush when the iterable is exhausted: as many frames come out as went in.  The first frame fixes the shape;
+    a frame that differs, a CPU tensor or another dtype raises before any launch.  ``emit = frames - 1`` yields
+    every frame as it arrives."""
+    from .streams import StudentStream, _check_rule
+    _check_rule(frames, emit)
+    stream = None
+    for frame in frames_iter:
+        if stream is None:
+            if not isinstance(frame, torch.Tensor) or frame.device.type != "cuda" or frame.dtype != torch.uint8 or \
+                    frame.dim() not in (3, 4):
+                raise RuntimeError("enhance_stream_u8 expects cuda uint8 frames [B,h,w] or [B,h,w,C]")
+            B, h, w = frame.shape[:3]
+            stream = StudentStream(model, B, h, w, frames, emit, frame.shape[3] if frame.dim() == 4 else 1, multiple,
+                                   "u8", device=frame.device)
+        out = stream.push(frame)
+        for k in range(out.shape[1]):
+            yield out[:, k]
+    if stream is not None:
+        out = stream.flush()
+        for k in range(out.shape[1]):
+            yield out[:, k]
 
 
 def to_tensor_u8(images: torch.Tensor) -> torch.Tensor:
