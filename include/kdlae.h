@@ -331,6 +331,50 @@ int kdlae_stream_push_f32(const float* frame, int B, int H, int W, int frames, v
                           void* stream);
 int kdlae_stream_advance(void* state, void* stream);
 
+/* Distillation labels: KDLAE-T (or Restormer) outputs as the targets of a KDLAE-S training step, without the
+ * folder of saved teacher images the reference's KDLAES.yml reads back.  The three entries move the data either
+ * side of a forward that stays untouched.  Items are the frames of a stack [B][F] in flat order j = b F + f; every
+ * entry works on the chunk j0 .. j0 + n - 1 (q = j - j0 below), so the teacher runs n frames at a time.  frames,
+ * rate, src and dst point at the whole stack, img, rate_map and hq at the chunk.
+ *
+ * kdlae_distill_expand_u8: frames u8 [B][F][h][w][channels] (channels 1 = gray, 3 / 4 = BGR / BGRA, alpha
+ * ignored) -> img f32 [n][3][H][W] and rate_map f32 [n][1][H][W], (H, W) = kdlae_padded_size(h, w, multiple), in one
+ * launch.  The gray value y of a pixel is its byte (channels 1) or cv2's 8-bit COLOR_BGR2GRAY,
+ *   y = (1868 B + 9617 G + 4899 R + 8192) >> 14,
+ * and all three channels of img hold (float)y / 255.0f, reflect-padded on the bottom/right: bit for bit
+ * kdlae_preprocess_u8 on the gray frame replicated to [h][w][3].  rate_map[q] is the constant rate[j], rate a device
+ * array of B F floats; rate and rate_map may both be null (a Restormer teacher takes no rate), then no map is written.
+ * kdlae_distill_expand_f32: the same for frames f32 [B][F][H][W] that are network inputs already (training crops; H
+ * and W multiples of 8): a bit copy into the three channels, and the rate map.  No padding, no clamp, no scale.
+ * kdlae_distill_collapse: hq f32 [n][3][Hp][Wp] -> items j0 .. of dst [B][F][h][w] (h <= Hp, w <= Wp: the top-left
+ * crop), f32 or, with dst_u8 != 0, u8; one launch either way.
+ *   mode KDLAE_DISTILL_FILE: the round trip through a lossless image file.  Per channel v = rintf(clamp(x, 0, 1) 255)
+ *     as kdlae_postprocess_u8 does; with src u8 [B][F][h][w][src_channels] (nullable), all three bytes become 0 where
+ *     the source pixel's gray value y is 0 (the black mask of kdlae_postprocess_u8 when its lq is the replicated
+ *     gray frame); then the three bytes, read as R, G, B, give g = (1868 v2 + 9617 v1 + 4899 v0 + 8192) >> 14.
+ *     dst = g (u8) or (float)g / 255.0f (f32).  The f32 form is what a grayscale float32 decode of the saved image
+ *     (the reference's imfrombytes(flag='grayscale', float32=True)) is modelled as: parity with a real cv2 encode /
+ *     decode is not pinned anywhere in this project.
+ *   mode KDLAE_DISTILL_MEAN: dst = ((x0 + x1) + x2) / 3.0f, every operation rounded on its own in fp32, no fused
+ *     multiply-add, no clamp, no mask (src is ignored); f32 output only.
+ * One thread per group of output pixels, no atomics: the result is a function of the inputs alone.  16-byte
+ * accesses of the fp32 tensors (4-byte stores of a u8 dst) when img and rate_map (expand_f32: and frames) sit on 16
+ * bytes and W % 4 == 0, or hq sits on 16 bytes, Wp % 4 == 0, w % 4 == 0 and dst sits on 16 (u8: 4) bytes; 4-byte
+ * (u8: single-byte) accesses otherwise, with the same bits.  A u8 frames / src may sit at any byte offset.
+ * Null frames, img, hq or dst, rate without rate_map or the reverse, n < 1, j0 < 0, j0 + n > B F, any size < 1,
+ * channels or src_channels outside {1, 3, 4}, an unknown mode, mode mean with dst_u8: KDLAE_EINVAL_CONFIG.  A frame
+ * smaller than its reflect padding, f32 H or W not a multiple of 8, h > Hp or w > Wp, an fp32 pointer off 4 bytes,
+ * more than 2^31 - 1 frames or pixels of one frame (the kernels keep a position inside a frame in 32 bits and
+ * everything else in 64): KDLAE_EINVAL_SHAPE.  Every check comes before the launch. */
+#define KDLAE_DISTILL_FILE 0
+#define KDLAE_DISTILL_MEAN 1
+int kdlae_distill_expand_u8(const uint8_t* frames, int B, int F, int h, int w, int channels, int multiple,
+                            const float* rate, int j0, int n, float* img, float* rate_map, void* stream);
+int kdlae_distill_expand_f32(const float* frames, int B, int F, int H, int W, const float* rate, int j0, int n,
+                             float* img, float* rate_map, void* stream);
+int kdlae_distill_collapse(const float* hq, int B, int F, int Hp, int Wp, int h, int w, int j0, int n, int mode,
+                           const uint8_t* src, int src_channels, void* dst, int dst_u8, void* stream);
+
 /* Measurement hook for bench.py (no effect on results).  When a probe class is armed, every
  * launch of that kernel class inside kdlae_t_forward is bracketed by a pair of HIP events on
  * `stream`; kdlae_t_probe_read synchronises those events and returns the summed device time (ms),

@@ -32,6 +32,7 @@ EXPORTS = (
     "kdlae_clip_plan", "kdlae_clip_gather", "kdlae_clip_blend", "kdlae_clip_blend_u8",
     "kdlae_stream_state_bytes", "kdlae_stream_reset", "kdlae_stream_push_u8", "kdlae_stream_push_f32",
     "kdlae_stream_advance",
+    "kdlae_distill_expand_u8", "kdlae_distill_expand_f32", "kdlae_distill_collapse",
     "kdlae_t_probe_arm", "kdlae_t_probe_read",
     "kdlae_t_debug_tap_count", "kdlae_t_debug_tap_info", "kdlae_t_debug_taps", "kdlae_t_debug_sr_fold",
     "kdlae_s_create", "kdlae_s_destroy", "kdlae_s_num_params", "kdlae_s_param_info",
@@ -259,6 +260,12 @@ def lib() -> ctypes.CDLL:
                                        c_void_p]
     L.kdlae_stream_push_f32.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
     L.kdlae_stream_advance.argtypes = [c_void_p, c_void_p]
+    L.kdlae_distill_expand_u8.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int,
+                                          c_void_p, c_void_p, c_void_p]
+    L.kdlae_distill_expand_f32.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
+                                           c_void_p, c_void_p]
+    L.kdlae_distill_collapse.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                         c_void_p, c_int, c_void_p, c_int, c_void_p]
     L.kdlae_t_probe_arm.argtypes = [c_void_p, c_int, c_int]
     L.kdlae_t_probe_read.argtypes = [c_void_p, ctypes.POINTER(c_double), ctypes.POINTER(c_int64),
                                      ctypes.POINTER(c_double), ctypes.POINTER(c_double)]

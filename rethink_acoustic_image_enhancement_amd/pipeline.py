@@ -22,6 +22,8 @@
 * ``enhance_stream_u8`` — the same cell for a source that delivers one frame at a time: a generator over the
   arriving frames that yields every frame enhanced, in order, at a fixed latency (streams.py: the window lives in
   a ring on the device and the steady state replays one HIP graph).
+* ``distill_clip_u8`` — KDLAE-T's output for every frame of a clip as the gray u8 labels KDLAE-S trains against
+  (distill.py: what the reference keeps as a folder of saved teacher images).
 * ``asdqe_scores`` / ``score_statistics`` / ``write_statistics_csv`` — ASDQE/ASDQE_test.py's
   ``infer`` + ``calculate_statistics`` + ``visualize_comparison`` CSV (:87-133).
 """
@@ -330,6 +332,15 @@ def enhance_clip_u8(model, clip: torch.Tensor, frames: int = 7, overlap: int = 2
     with torch.no_grad():
         return clips.clip_blend_u8(model._clip_windows(x, plan, frames, overlap, window_batch), B, T, h, w, frames,
                                    overlap, table)
+
+
+def distill_clip_u8(teacher, clip: torch.Tensor, denoise_rate, teacher_batch: int = 16, tile=None,
+                    tile_overlap: int = 32, window="uniform") -> torch.Tensor:
+    """The label folder of KDLAES.yml for one clip, without the folder: u8 [B,T,h,w] (gray) or [B,T,h,w,C] (cv2 BGR /
+    BGRA) -> u8 [B,T,h,w], the gray bytes an image file of the teacher's ``enhance_u8`` output of every frame holds
+    (``distill.teacher_labels_u8``: ``teacher_batch`` frames a forward, expanded and collapsed on the device)."""
+    from . import distill
+    return distill.teacher_labels_u8(teacher, clip, denoise_rate, teacher_batch, tile, tile_overlap, window)
 
 
 def enhance_stream_u8(model, frames_iter, frames: int = 7, emit: int | None = None, multiple: int = 32):

@@ -762,6 +762,44 @@ class KDLAESTrainer(_TrainingState):
         return res
 
 
+class DistillTrainer(KDLAESTrainer):
+    """``KDLAESTrainer`` whose targets are computed by a teacher on the device inside the step
+    (``distill.teacher_labels``) instead of being read from the folder of saved teacher outputs that KDLAES.yml's
+    ``dataroot_gt`` names.  ``teacher``: a ``KDLAE_teacher`` or ``Restormer`` in eval mode on the student's device;
+    its parameters are read, never written, and it is not part of the training state (``validate``,
+    ``training_state`` and ``resume_training`` are the parent's).  ``denoise_rate``, ``label_mode`` (``"mean"``:
+    no quantisation; ``"file"``: the saved-image round trip) and ``teacher_batch`` are ``teacher_labels``'
+    arguments; everything else is ``KDLAESTrainer``'s."""
+
+    def __init__(self, student, teacher, denoise_rate, label_mode="mean", teacher_batch=16, **kwargs):
+        from . import distill
+        if label_mode not in distill.MODES:
+            raise RuntimeError(f"label_mode must be one of {sorted(distill.MODES)}, got {label_mode!r}")
+        if teacher.training:
+            raise RuntimeError("DistillTrainer: the teacher must be in eval mode (call .eval() first)")
+        super().__init__(student, **kwargs)
+        self.teacher, self.denoise_rate = teacher, denoise_rate
+        self.label_mode, self.teacher_batch = label_mode, int(teacher_batch)
+        self.labels = None
+
+    def make_labels(self, frames):
+        """The teacher's targets for ``frames`` (u8 [B,F,h,w(,C)] or f32 [B,F,H,W]) in a buffer kept across steps."""
+        from . import distill
+        shape = tuple(frames.shape[:4])
+        if self.labels is None or tuple(self.labels.shape) != shape or self.labels.device != frames.device:
+            self.labels = torch.empty(shape, dtype=torch.float32, device=frames.device)
+        return distill.teacher_labels(self.teacher, frames, self.denoise_rate, self.label_mode, self.teacher_batch,
+                                      out=self.labels)
+
+    def optimize_parameters(self, lq, clean=None):
+        """One step against the teacher's labels of ``clean`` (default: of ``lq`` itself; ``clean`` lets ``lq`` be
+        degraded by ``augment.train_inputs`` / ``mask_frames`` while the teacher sees the undegraded frames).
+        Mixup, if configured, is applied after the labels are made; then the parent's forward_backward and step."""
+        gt = self.make_labels(clean if clean is not None else lq)
+        lq, gt = self.feed_train_data(lq, gt)
+        return super().optimize_parameters(lq, gt)
+
+
 # ------------------------------------------------------------------ ASDQE (Train/ASDQE.py)
 def _bn_modules(model):
     return [m for m in model.modules() if isinstance(m, torch.nn.BatchNorm2d)]
