@@ -13,6 +13,26 @@
  * call makes the handle's device current and restores the caller's device
  * before returning.
  *
+ * Caller's stream, for every entry that takes a `stream`: all its device
+ * work (kernels, zero fills, device copies) is ordered on that stream and
+ * nothing goes to the null stream; a stream the library owns (the training
+ * backwards' side stream) waits on `stream` before its first launch and is
+ * joined back into it before the call returns; the call neither waits on
+ * the host nor allocates, so it returns while `stream` is still busy and
+ * can be captured into a HIP graph on it (memory is zeroed by a kernel of
+ * the library's own, so every node of such a graph is a kernel).  While
+ * `stream` is being captured, kdlae_tt_backward and kdlae_st_backward keep
+ * every launch on it, as under KDLAE_DEBUG=train_serial (same bits): the
+ * side stream and the handle's events outlive any graph and are never
+ * drawn into a caller's capture.  The exceptions: kdlae_*_set_param,
+ * *_commit_params, *_prepare, *_create and *_destroy (host data,
+ * allocation, synchronous), kdlae_data_sample (may wait on the host, not
+ * for capture), kdlae_tt_mark_sync (a host wait), kdlae_tt_backward_marked
+ * (asynchronous and ordered, but its marks are handle-owned events: under
+ * capture it is refused with KDLAE_ESTATE before any launch) and the
+ * kdlae_debug_* / kdlae_t_debug_* self-test entries.
+ * tests/test_caller_stream_gpu.py holds every entry to this.
+ *
  * Error handling: every call returns KDLAE_OK (0) or one of the codes
  * below; kdlae_last_error() returns a thread-local message describing the
  * last failure on the calling thread.
@@ -821,7 +841,8 @@ int kdlae_train_mask_frames(const float* src, float* dst, int B, int F, int H, i
  * when (double)max(counts[0], counts[1]) / count_n > count_thr, decided on the device; then (x - mean[c']) / std[c']
  * in fp32 by destination channel where given (each nullable).  dst must not overlap src.  `items` is a host
  * table; it is validated, copied to `table` (device, n_items * sizeof(kdlae_data_item) bytes) on the stream and
- * served by one launch. */
+ * served by one launch.  The copy reads pageable host memory, so this one entry may wait on the host until the
+ * stream has reached it, and is not for graph capture; its result does not depend on the stream it is given. */
 typedef struct {
   const void* src;        /* device, u8 or fp32 */
   float* dst;             /* device fp32 [C, h', w'] contiguous */

@@ -440,7 +440,7 @@ int asdqe_train_backward(asdqe_train_handle* h, const float* theta, const float*
   DeviceGuard dg(h->device);
   c.gr = c.buf(c.pl.gtmp);
   // zero: the pad floats and the BatchNorm-fed conv biases, whose gradient is exactly zero
-  HIPCHK(hipMemsetAsync(c.gr, 0, (size_t)h->lay.total * sizeof(float), c.s));
+  HIPCHK(zero_fill(c.gr, (size_t)h->lay.total * sizeof(float), c.s));
   h->last.valid = false;  // a forward's activations serve one backward
   TRY(net_bwd(c, dscore));
   HIPCHK(tr::launch_grad_commit(c.gr, grad, h->lay.total, accumulate ? 1 : 0, c.s));

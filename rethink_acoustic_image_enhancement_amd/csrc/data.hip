@@ -200,7 +200,7 @@ int kdlae_data_count(const float* x, int B, int64_t n_per_sample, int32_t* count
   if (!x || !counts) return fail(KDLAE_EINVAL_CONFIG, "kdlae_data_count: null x or counts");
   if (B <= 0 || B > data::kMaxItems || n_per_sample <= 0 || n_per_sample > INT32_MAX)
     return fail(KDLAE_EINVAL_SHAPE, "kdlae_data_count: B must be 1..65535 and n_per_sample 1..2^31-1");
-  HIPCHK(hipMemsetAsync(counts, 0, sizeof(int32_t) * 2 * (size_t)B, (hipStream_t)stream));
+  HIPCHK(zero_fill(counts, sizeof(int32_t) * 2 * (size_t)B, (hipStream_t)stream));
   const dim3 grid(data::grid_for(n_per_sample, data::kMaxBlocks / B), B);
   hipLaunchKernelGGL(data::data_count_kernel, grid, dim3(data::kThreads), 0, (hipStream_t)stream, x,
                      (long long)n_per_sample, counts);

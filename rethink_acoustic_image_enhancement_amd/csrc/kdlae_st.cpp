@@ -482,9 +482,9 @@ int kdlae_st_backward(kdlae_st_handle* h, const float* theta, const float* dout,
   if ((int64_t)c.pl.total > workspace_bytes) return fail(KDLAE_ESTATE, "training workspace too small");
   DeviceGuard dg(h->device);
   c.main_s = c.s;
-  TRY(h->side.acquire(&c.side));
-  HIPCHK(hipMemsetAsync(grad, 0, (size_t)h->lay.total * sizeof(float), c.s));  // the pad floats stay zero
-  HIPCHK(hipMemsetAsync(c.buf(c.pl.zb), 0, 64 * sizeof(float), c.s));
+  TRY(h->side.acquire(&c.side, c.main_s));
+  HIPCHK(zero_fill(grad, (size_t)h->lay.total * sizeof(float), c.s));  // the pad floats stay zero
+  HIPCHK(zero_fill(c.buf(c.pl.zb), 64 * sizeof(float), c.s));
   return net_bwd(c, h->x, dout);
 }
 

@@ -1056,7 +1056,7 @@ int net_bwd(Ctx& c, const float* dhq, const float* dsr, bool has_dsr) {
   if (trunk) {
     dhq_h = c.alloc(P1 * oc);
     if (dhq) LAUNCH(tr::launch_nchw_to_nhwc(dhq, oc, B, (long long)H * W, dhq_h, oc, 0, c.s));
-    else LAUNCH(hipMemsetAsync(dhq_h, 0, P1 * oc * sizeof(float), c.s));
+    else LAUNCH(kdlae::zero_fill(dhq_h, P1 * oc * sizeof(float), c.s));
   }
   if (cf.static_train && has_dsr) {
     TRY(sr_bwd(c, dsr, dhq_h));
@@ -1209,7 +1209,7 @@ void ctx_init(Ctx& c, const kdlae_tt_handle* h, void* ws, size_t ws_bytes, bool 
 // the backward's side stream and stage_bwd's two block events, created once per handle on its device
 // (KDLAE_DEBUG=train_serial: neither; every launch on the caller's stream, same results)
 int use_side_stream(Ctx& c, kdlae_tt_handle* h) {
-  TRY(h->side.acquire(&c.side));
+  TRY(h->side.acquire(&c.side, c.main_s));
   for (hipEvent_t& ev : h->ev_blk)
     if (c.side && !ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
   return KDLAE_OK;
@@ -1260,10 +1260,12 @@ int bwd_run(kdlae_tt_handle* h, const float* theta, const float* dhq, const floa
   c.off = h->sv.fwd_end;
   c.record_marks = written != nullptr;
   c.touch = written;
+  if (written && kdlae::stream_capturing(stream))  // the marks are handle-owned events: never part of a caller's graph
+    return fail(KDLAE_ESTATE, "kdlae_tt_backward_marked cannot be captured into a graph: use kdlae_tt_backward");
   if (kdlae::debug_flag("train_trace")) c.trace = &h->trace;
   int rc = use_side_stream(c, h);
   if (rc) return rc;
-  hipError_t e = hipMemsetAsync(grad, 0, (size_t)h->lay.total * sizeof(float), stream);
+  hipError_t e = kdlae::zero_fill(grad, (size_t)h->lay.total * sizeof(float), stream);
   if (e != hipSuccess) return fail(KDLAE_EHIP, hipGetErrorString(e));
   rc = net_bwd(c, dhq, dsr, has_dsr);
   if (rc == KDLAE_OK) rc = flush_all(c);

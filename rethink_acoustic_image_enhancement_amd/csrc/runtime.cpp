@@ -15,6 +15,23 @@ int fail(int code, const std::string& msg) {
   return code;
 }
 
+template <typename T>
+__global__ void zero_fill_kernel(T* p, long long n) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+    p[i] = T{};
+}
+
+hipError_t zero_fill(void* p, size_t bytes, hipStream_t stream) {
+  if (bytes == 0) return hipSuccess;
+  if (!p || ((uintptr_t)p & 3) || (bytes & 3)) return hipErrorInvalidValue;
+  const bool vec = !((uintptr_t)p & 15) && !(bytes & 15);
+  const long long n = (long long)(bytes / (vec ? 16 : 4));
+  const unsigned blocks = (unsigned)std::min<long long>((n + 255) / 256, 4096);
+  if (vec) hipLaunchKernelGGL(zero_fill_kernel<uint4>, dim3(blocks), dim3(256), 0, stream, static_cast<uint4*>(p), n);
+  else hipLaunchKernelGGL(zero_fill_kernel<uint32_t>, dim3(blocks), dim3(256), 0, stream, static_cast<uint32_t*>(p), n);
+  return hipGetLastError();
+}
+
 bool debug_flag(const char* name) {
   const char* e = getenv("KDLAE_DEBUG");
   if (!e) return false;

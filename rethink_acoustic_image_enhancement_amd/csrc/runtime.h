@@ -24,6 +24,13 @@ int fail(int code, const std::string& msg);
 // of flag names (include/kdlae.h lists them).  They select between kernel schedules that give the
 // same bits (the GPU tests compare them); nothing else in the library reads the environment.
 bool debug_flag(const char* name);
+// Zero `bytes` bytes at p on `stream` with a kernel of the library's own (16-byte stores where p and bytes allow,
+// 4-byte ones otherwise; p and bytes must be multiples of 4, hipErrorInvalidValue if not).  Used instead of
+// hipMemsetAsync wherever an entry zeroes memory, so that a captured graph of the call holds kernel nodes only.
+// Observed with hipMemsetAsync: the first replay of such a graph was right and the second was not, in exactly
+// the five entries that zeroed memory; that the memset node is what misbehaves is supposed, not shown
+// (tests/test_caller_stream_gpu.py, S3).
+hipError_t zero_fill(void* p, size_t bytes, hipStream_t stream);
 
 #define HIPCHK(x)                                                                                  \
   do {                                                                                             \

@@ -145,7 +145,8 @@ extern "C" int64_t kdlae_stream_state_bytes(int B, int frames, int H, int W) {
 
 extern "C" int kdlae_stream_reset(void* state, void* stream) {
   if (!state) return fail(KDLAE_EINVAL_CONFIG, "kdlae_stream_reset: null argument");
-  HIPCHK(hipMemsetAsync(state, 0, kStreamHeader, (hipStream_t)stream));
+  if (((uintptr_t)state & 7) != 0) return fail(KDLAE_EINVAL_SHAPE, "kdlae_stream_reset: state must sit on 8 bytes");
+  HIPCHK(zero_fill(state, kStreamHeader, (hipStream_t)stream));
   return KDLAE_OK;
 }
 

@@ -46,6 +46,17 @@ struct LastForward {
   }
 };
 
+// true while `s` is being captured into a graph (an error answer, the null stream beside another thread's
+// capture, counts as no)
+inline bool stream_capturing(hipStream_t s) {
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &st) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return st != hipStreamCaptureStatusNone;
+}
+
 // A backward's side stream (non-blocking) with its fork and join events: launches that only read what
 // the main stream leaves alone until the next join (weight and bias gradients) run there, beside the
 // input-gradient chain on the caller's stream.  Lives in the handle; destroyed with it.
@@ -58,9 +69,12 @@ struct SideStream {
     if (s) (void)hipStreamDestroy(s);
   }
   // *use = this, created on the current device at the first call; *use stays as it is (null: every
-  // launch on the caller's stream, same results) under KDLAE_DEBUG=train_serial
-  int acquire(SideStream** use) {
+  // launch on the caller's stream, same results) under KDLAE_DEBUG=train_serial, and while `main` is being
+  // captured into a graph: the side stream and the handle's events outlive any graph, so they are never
+  // drawn into a caller's capture (include/kdlae.h, "Caller's stream")
+  int acquire(SideStream** use, hipStream_t main) {
     if (debug_flag("train_serial")) return KDLAE_OK;
+    if (stream_capturing(main)) return KDLAE_OK;
     if (!s) {
       HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
       HIPCHK(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));

@@ -152,37 +152,42 @@ def test_t_forward_sr_scratch_independence(name, shape):
     check_scratch_independence(call, call.reference())
 
 
+class TRates(Call):
+    """kdlae_t_forward_rates with the sr head: R rates of B images, scalars (is_map 0) or maps (is_map 1)"""
+
+    def __init__(self, m, B, R, H, W, is_map):
+        self.m, self.shape, self.is_map = m, (B, R, H, W), is_map
+        self.eng = m.engine(DEV)
+        self.eng.sync_params(m, stream().value or 0)
+        self.img = _images("ws:rates:img", (B, 3, H, W))
+        self.rates = _images(f"ws:rates:{is_map}", (R, B, 1, H, W) if is_map else (R, B))
+        n = R * B * 3 * H * W
+        self.out_numels = (n, 4 * n)
+        self.ws_bytes = _lib.lib().kdlae_t_rates_workspace_bytes(self.eng.handle, B, R, H, W, 1)
+        self.operands = {"img": self.img, "rates": self.rates}
+
+    def steps(self, arena):
+        B, R, H, W = self.shape
+        return [("kdlae_t_forward_rates", lambda nbytes: _lib.lib().kdlae_t_forward_rates(
+            self.eng.handle, vp(self.img), vp(self.rates), self.is_map, B, R, H, W, vp(arena.outs[0]),
+            vp(arena.outs[1]), vp(arena.ws), nbytes, stream()))]
+
+    def reference(self):
+        with torch.no_grad():
+            ref = self.m.forward_rates(self.img, self.rates, sr=True)
+        torch.cuda.synchronize()
+        return [ref["hq"], ref["sr"]]
+
+
 def test_t_forward_rates_scratch_independence():
     """kdlae_t_forward_rates (its exact fit: test_rate_sweep_gpu.test_no_overrun_at_64_rates_and_short_workspace_
     refused): three rates of three 16 x 24 images, scalars and maps."""
     m = _teacher("default")
-    B, R, H, W = 3, 3, 16, 24
-    L = _lib.lib()
-
-    class Rates(Call):
-        def __init__(self, is_map):
-            self.is_map = is_map
-            self.eng = m.engine(DEV)
-            self.eng.sync_params(m, stream().value or 0)
-            self.img = _images("ws:rates:img", (B, 3, H, W))
-            self.rates = _images(f"ws:rates:{is_map}", (R, B, 1, H, W) if is_map else (R, B))
-            n = R * B * 3 * H * W
-            self.out_numels = (n, 4 * n)
-            self.ws_bytes = L.kdlae_t_rates_workspace_bytes(self.eng.handle, B, R, H, W, 1)
-            self.operands = {"img": self.img, "rates": self.rates}
-
-        def steps(self, arena):
-            return [("kdlae_t_forward_rates", lambda nbytes: L.kdlae_t_forward_rates(
-                self.eng.handle, vp(self.img), vp(self.rates), self.is_map, B, R, H, W, vp(arena.outs[0]),
-                vp(arena.outs[1]), vp(arena.ws), nbytes, stream()))]
-
     for is_map in (0, 1):
-        call = Rates(is_map)
-        with torch.no_grad():
-            ref = m.forward_rates(call.img, call.rates, sr=True)
-        torch.cuda.synchronize()
+        call = TRates(m, 3, 3, 16, 24, is_map)
+        ref = call.reference()
         check_exact_fit(call)
-        check_scratch_independence(call, [ref["hq"], ref["sr"]])
+        check_scratch_independence(call, ref)
 
 
 @pytest.mark.parametrize("name", ["default", "dim16"])
