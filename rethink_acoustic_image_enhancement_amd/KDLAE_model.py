@@ -474,6 +474,59 @@ class KDLAE_teacher(nn.Module):
         sr = tiling.tile_blend(st_sr, B, H, W, tile, tile_overlap, 2, window=win_sr) if has_sr else None
         return {"hq": hq, "sr": sr}
 
+    # ------------------------------------------------------------------ self-ensemble
+    def forward_ensemble(self, input, modes="d8", ens_batch=8):
+        """Geometric self-ensemble (the "x8" test-time trick): ``forward`` on the dihedral views of the image and of
+        its rate map, every output turned back and the results averaged (ensemble.py and include/kdlae_ensemble.h
+        state the modes, the sum order and the slot layout).  ``modes``: ``"d8"`` (all eight), ``"flips"`` (the four
+        that keep the shape) or an iterable of modes 0..7.  The views of each input are gathered with one launch,
+        go through this module's own inference forward ``ens_batch`` views of the whole batch at a time (runs of
+        consecutive views of one shape; with H == W any views), so every full chunk replays one HIP graph, and one
+        merge launch per output writes the result.
+
+        Returns ``{"hq": [B,C,H,W], "sr": [B,C,2H,2W] or None}``, bit for bit the host loop (``torch.rot90`` /
+        ``torch.flip`` of image and rate map, ``forward``, the inverse, ``E.add_`` in ascending mode order, one
+        ``E.div_``) for every ``ens_batch``; ``modes=(0,)`` equals ``forward``.  The mean over the views is a
+        different function of the image from ``forward``, not an approximation of it that carries a bound.
+        Inference only (eval mode, no autograd graph).  A chunk is one forward at batch ``ens_batch * B`` and the
+        workspace grows with it: lower ``ens_batch`` when that many images do not fit."""
+        self._check_inference_input(input["img"], "forward_ensemble")
+        with torch.no_grad():
+            return self._forward_ensemble(input["img"], input.get("denoise_rate"), modes, ens_batch)
+
+    def _forward_ensemble(self, img, rate, modes, ens_batch, flat=None):
+        """``flat``: as in ``_forward_eager`` (a trainer's flat parameters; always launched one by one)."""
+        from . import ensemble
+        ci, oc = self._cfg["inp_channels"], self._cfg["out_channels"]
+        if img.dim() != 4 or img.shape[1] != ci:
+            raise RuntimeError(f"expected img [B,{ci},H,W], got {tuple(img.shape)}")
+        B, _, H, W = img.shape
+        mask = ensemble.mode_mask(modes)              # refuses bad modes / ens_batch / shapes before any launch
+        ensemble.ens_chunks(mask, H, W, ens_batch)
+        if H % 8 or W % 8:
+            raise RuntimeError(f"forward_ensemble needs H and W divisible by 8, got {H}x{W}")
+        cat = self._cfg["params"] == "cat"
+        if cat and (rate is None or tuple(rate.shape) != (B, 1, H, W)):
+            raise RuntimeError(f"denoise_rate must be [B,1,H,W]={B, 1, H, W}, got "
+                               f"{tuple(rate.shape) if rate is not None else None}")
+        dev = img.device
+        has_sr = self.static == "train"
+        g_img = ensemble.ens_gather(img.detach().to(torch.float32), mask)
+        g_rate = ensemble.ens_gather(rate.detach().to(device=dev, dtype=torch.float32), mask) if cat else None
+        graphed = flat is None and self.hip_graphs and not torch.cuda.is_current_stream_capturing()
+
+        def run(ins, outs):
+            if graphed:
+                self._forward_graphed(ins[0], ins[1], out=tuple(outs))
+            else:
+                self._forward_eager(ins[0], ins[1], flat=flat, out=tuple(outs))
+
+        st_hq, st_sr = ensemble.run_views(run, mask, B, H, W, ens_batch, [(g_img, ci), (g_rate, 1)],
+                                          [oc, oc if has_sr else None], [1, 2])
+        hq = ensemble.ens_merge(st_hq, B, H, W, mask)
+        sr = ensemble.ens_merge(st_sr, B, 2 * H, 2 * W, mask) if has_sr else None
+        return {"hq": hq, "sr": sr}
+
     # ------------------------------------------------------------------ rate sweep
     def _check_inference_input(self, x, what):
         if self.dual_pixel_task:
@@ -759,6 +812,13 @@ class Restormer(KDLAE_teacher):
         with torch.no_grad():
             return self._forward_tiled(inp_img, None, tile, tile_overlap, tile_batch, window=window)["hq"]
 
+    def forward_ensemble(self, inp_img, modes="d8", ens_batch=8):
+        """``forward`` on the dihedral views of the image, turned back and averaged on the device
+        (``KDLAE_teacher.forward_ensemble`` states the rule, ``modes`` and ``ens_batch``): ``[B,C,H,W] -> [B,C,H,W]``."""
+        self._check_inference_input(inp_img, "forward_ensemble")
+        with torch.no_grad():
+            return self._forward_ensemble(inp_img, None, modes, ens_batch)["hq"]
+
     def forward_rates(self, *args, **kwargs):
         raise RuntimeError("Restormer has no denoise_rate input: forward_rates is KDLAE_teacher's")
 
@@ -902,6 +962,30 @@ class KDLAE_student(nn.Module):
             self._forward_eager(clips.clip_gather(x_c, frames, overlap, first, count),
                                 out=staged[first:first + count])
         return staged
+
+    def forward_ensemble(self, x, modes="d8", ens_batch=8):
+        """Geometric self-ensemble of ``forward``: ``x [B,F,H,W] -> [B,F,H,W]``, the frames being the channel axis
+        of the views (every frame of a window is flipped and turned alike).  The views are gathered with one
+        launch, go through this module's own inference forward ``ens_batch`` views of the whole batch at a time
+        (runs of consecutive views of one shape) into a staging tensor, and one merge launch writes the mean
+        (ensemble.py and include/kdlae_ensemble.h state the modes, the sum order and the layout).
+
+        Bit for bit the host loop (``torch.rot90`` / ``torch.flip``, ``forward``, the inverse, ``E.add_`` in
+        ascending mode order, one ``E.div_``) for every ``ens_batch``; ``modes=(0,)`` equals ``forward``.  A
+        different function of the frames from ``forward``, not an approximation of it that carries a bound.
+        Inference only (eval mode, no autograd graph)."""
+        from . import ensemble
+        if self.training:
+            raise RuntimeError("KDLAE_student.forward_ensemble is inference-only: call .eval() first")
+        self._check_input(x)
+        B, Fr, H, W = x.shape
+        mask = ensemble.mode_mask(modes)
+        ensemble.ens_chunks(mask, H, W, ens_batch)     # refuses a bad ens_batch before any launch
+        with torch.no_grad():
+            g_x = ensemble.ens_gather(x.detach().to(torch.float32), mask)
+            staged, = ensemble.run_views(lambda ins, outs: self._forward_eager(ins[0], out=outs[0]), mask, B, H, W,
+                                         ens_batch, [(g_x, Fr)], [Fr], [1])
+            return ensemble.ens_merge(staged, B, H, W, mask)
 
     def stream(self, batch, h, w, frames=7, emit=None, channels=1, multiple=32, dtype="u8"):
         """A ``streams.StudentStream`` on this module: frames of ``batch`` parallel sources pushed one at a time,

@@ -71,6 +71,10 @@ EXPORTS = (
     "kdlae_debug_head_train",
 )
 
+# The entry points include/kdlae_ensemble.h declares (checked by tests/test_ensemble.py): a header and a tuple of
+# their own, include/kdlae.h and EXPORTS stay as they are.
+ENSEMBLE_EXPORTS = ("kdlae_ens_gather", "kdlae_ens_merge")
+
 
 class TConfig(ctypes.Structure):
     """kdlae_t_config (include/kdlae.h) = KDLAE_teacher ctor kwargs (KDLAE_model.py:205-218)."""
@@ -404,6 +408,9 @@ def lib() -> ctypes.CDLL:
         getattr(L, f).argtypes = [c_void_p, c_void_p]
     L.kdlae_debug_train_blocks.argtypes = [c_int, c_int64, c_int, c_int, c_int64]
     L.kdlae_debug_gemm_variant.argtypes = [c_int, c_int, ctypes.POINTER(c_int)]
+    for name in ENSEMBLE_EXPORTS:   # (src, dst, N, C, H, W, mode_mask, stream)
+        getattr(L, name).argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]
+        getattr(L, name).restype = c_int
     for name in EXPORTS:
         if not name.endswith(("_last_error", "_abi_version", "_workspace_bytes", "_padded_size", "_num_floats",
                               "_scratch_floats", "_scratch_bytes", "_state_bytes", "_params_numel", "_mark_lo", "_num_stat_floats",

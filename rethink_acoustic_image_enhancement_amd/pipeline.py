@@ -7,6 +7,8 @@
   (``kdlae_preprocess_u8`` / ``kdlae_postprocess_u8``); images never round-trip through the host.
 * ``enhance_tiled_u8`` — the same cell for images too large for one forward: ``KDLAE_teacher.forward_tiled``
   between the same pre and post kernels (tiling.py).
+* ``enhance_ensemble_u8`` — the same cell with geometric self-ensemble: ``forward_ensemble`` (the eight dihedral
+  views, merged on the device; ensemble.py) between the same pre and post kernels.
 * ``enhance_rates_u8`` / ``enhance_auto_u8`` — the notebook's "pick a rate, look, pick again" loop as one
   call: R rates of the same images through ``KDLAE_teacher.forward_rates`` (the rate-independent trunk runs
   once), every candidate post-processed as the notebook saves it, and — ``enhance_auto_u8`` — scored by
@@ -119,6 +121,24 @@ def enhance_tiled_u8(model, images: torch.Tensor, denoise_rate, tile: int = 512,
                               images), None
     img, rmap = preprocess_u8(images, denoise_rate, multiple, bgr)
     pred = model.forward_tiled({"img": img, "denoise_rate": rmap}, tile, tile_overlap, tile_batch, window)
+    hq = postprocess_u8(pred["hq"], h, w, 1, images)
+    sr = postprocess_u8(pred["sr"], h, w, 2, images) if pred.get("sr") is not None else None
+    return hq, sr
+
+
+def enhance_ensemble_u8(model, images: torch.Tensor, denoise_rate, modes="d8", ens_batch: int = 8,
+                        bgr: bool = False, multiple: int = 8):
+    """``enhance_u8`` with geometric self-ensemble: the same pre- and post-processing around
+    ``forward_ensemble`` on the padded tensor (the dihedral views gathered, batched through the forward and merged
+    on the device; ensemble.py) -> (hq u8, sr u8 or None).  Serves ``KDLAE_teacher`` and ``Restormer`` (which
+    ignores ``denoise_rate``).  The mean over the views is a different function of the image from ``enhance_u8``'s
+    output, not an approximation of it; ``modes=(0,)`` equals it."""
+    B, h, w, C = images.shape
+    if _is_restormer(model):
+        img, _ = preprocess_u8(images, None, multiple, bgr)
+        return postprocess_u8(model.forward_ensemble(img, modes, ens_batch), h, w, 1, images), None
+    img, rmap = preprocess_u8(images, denoise_rate, multiple, bgr)
+    pred = model.forward_ensemble({"img": img, "denoise_rate": rmap}, modes, ens_batch)
     hq = postprocess_u8(pred["hq"], h, w, 1, images)
     sr = postprocess_u8(pred["sr"], h, w, 2, images) if pred.get("sr") is not None else None
     return hq, sr

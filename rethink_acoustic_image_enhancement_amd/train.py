@@ -1390,7 +1390,8 @@ class _ImageCleanTrainer(_TrainingState):
 
     @torch.no_grad()
     def validate(self, batches, window_size=8, crop_border=0, use_image=False, use_ema=None, metrics=("psnr",),
-                 niqe=False, niqe_params=None, tile=None, tile_overlap=32, tile_batch=16, tile_window="uniform"):
+                 niqe=False, niqe_params=None, tile=None, tile_overlap=32, tile_batch=16, tile_window="uniform",
+                 ensemble=None, ens_batch=8):
         """ImageCleanModel.nondist_validation with pad_test (image_restoration_model.py:226-348) over
         ``(lq, gt)`` pairs, ``lq = {'img', 'denoise_rate'}``, ``gt = {'hq', 'sr'}`` (RestormerTrainer: two
         tensors, and only the ``*_hq`` results): reflect-pad ``img`` and the
@@ -1411,11 +1412,20 @@ class _ImageCleanTrainer(_TrainingState):
         so its metrics are not comparable digit for digit with ``tile=None``, today's path.  ``tile_window``:
         the blend window of the tiled forward (``forward_tiled``'s ``window``); not read without ``tile``.
 
+        ``ensemble``: geometric self-ensemble at evaluation, the usual setting of reported PSNR / SSIM: ``"d8"``,
+        ``"flips"`` or an iterable of modes 0..7 (``forward_ensemble``'s ``modes``, ``ens_batch`` views of the batch
+        a forward).  The padded image goes through the views' forwards and one merge per output (with the weights
+        chosen below; the padded sizes must then be multiples of 8) instead of one ``kdlae_t_forward``.  The mean
+        over the views is a different function of the image, so its metrics are not comparable digit for digit
+        with ``ensemble=None``, today's path.  Not to be combined with ``tile``.
+
         ``use_ema=None``: the EMA weights when ``ema_decay > 0`` (net_g_ema, :242-248), else the live ones.
         The chosen flat vector is packed straight into the module's inference handle; the trainer's buffers,
         the training engine and the module's parameters are not written, so training continues bit for bit."""
         from .metrics import load_niqe_params, niqe_batch, psnr_batch, ssim_batch
         want_psnr, want_ssim = _val_metrics(metrics)
+        if ensemble is not None and tile is not None:
+            raise RuntimeError("validate: ensemble= and tile= cannot be combined")
         niqe_p, n_hqs, n_srs = (load_niqe_params(niqe_params) if niqe else None), [], []
         if use_ema is None:
             use_ema = self.theta_ema is not None
@@ -1431,7 +1441,9 @@ class _ImageCleanTrainer(_TrainingState):
             img_p = _reflect_pad(img.to(torch.float32), window_size)
             rate_p = _reflect_pad(rate.to(device=img.device, dtype=torch.float32), window_size) if rate is not None \
                 else None
-            if tile is None:
+            if ensemble is not None:
+                out = self.model._forward_ensemble(img_p, rate_p, ensemble, ens_batch, flat=flat)
+            elif tile is None:
                 out = self.model._forward_eager(img_p, rate_p, flat=flat)
             else:
                 out = self.model._forward_tiled(img_p, rate_p, tile, tile_overlap, tile_batch, flat=flat,
